@@ -21,9 +21,12 @@ sharded over the ranks: cyclic image ownership for detection, one RCCL all-gathe
 block-cyclic pair ownership for matching (SuperGlue, 100 Sinkhorn iterations by default), ragged gather of the match
 lists. Strong scaling: ``value`` = the scene's pairs / max-over-ranks time.
 
-Rank 0 prints ONE JSON line: the whole-job rate, the roofline of the dominant kernel (measured live with HIP events
-on the launch stream), at N = 1 a CPU baseline (the oracle, timed on a bounded sample of the same workload), a
-``parity_check`` of the GPU result against that oracle run on the same two images, and ``secondary`` rates.
+Rank 0 prints ONE JSON line: the whole-job rate and ``ms_per_step``, the time of one timed step. A plain run does nothing
+else: set up, warm up, time ``--steps`` steps, print. ``--full`` adds the roofline of the dominant kernel (measured live
+with HIP events on the launch stream), at N = 1 a CPU baseline (the oracle, timed on a bounded sample of the same
+workload), a ``parity_check`` of the GPU result against that oracle run on the same two images, and ``secondary`` rates.
+``--dump-outputs DIR`` writes the last timed step's outputs as ``DIR/<name>.npy`` (seeded inputs: identical from run to
+run, so two builds can be compared output for output).
 """
 
 from __future__ import annotations
@@ -567,10 +570,16 @@ def parse_args(argv=None):
     ap.add_argument("--arithmetic", choices=["f32", "bf16x3", "f16x2"], default="f32",
                     help="f32 (default): the headline, exact fp32 everywhere. bf16x3 / f16x2: the WHOLE run under both opt-in switches (GTSFM_ATTENTION_MATH and "
                          "GTSFM_GEMM_MATH; DESIGN.md section 4) -- a side measurement of the same step protocol, labelled in `dtype` and `config.arithmetic`, never the headline")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the secondary rates")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beyond the headline: per-kernel rooflines, the CPU baseline with the parity check against it, "
+                         "and the secondary rates (a plain run sets up, warms up, times --steps steps and prints the line)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last step computed as DIR/<name>.npy (float32; outputs larger than their "
+                         "share of 64 MB as a fixed, seeded sample of rows)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline and the parity check")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: skip the secondary rates")
     ap.add_argument("--no-roofline", action="store_true",
-                    help="skip the per-kernel roofline micro-launches (for rocprofv3 --kernel-trace runs whose stats should hold the workload's launches only)")
+                    help="with --full: skip the per-kernel roofline micro-launches (for rocprofv3 --kernel-trace runs whose stats should hold the workload's launches only)")
     ap.add_argument("--details-file", default=DETAILS_FILE,
                     help="where the full record goes (secondary legs, every kernel's roofline, notes); stdout carries only the < 4 KB headline line. '' = nowhere")
     ap.add_argument("--dump-matches", type=int, default=0, help="1: add match_digest (SHA-1 over the last step's (K,2) match arrays in pair order) to the line")
@@ -590,8 +599,12 @@ def parse_args(argv=None):
         ap.error("--mode scene needs a matcher")
     if scene and args.pair_definition != "exhaustive":
         ap.error("--mode scene matches the exhaustive pairs of one scene")
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.plumbing_only:
         args.backend = "gloo"
+    if not args.full:  # a plain run measures the headline only
+        args.no_cpu_baseline = args.no_secondary = args.no_roofline = True
     return args
 
 
@@ -630,6 +643,54 @@ def matches_to_numpy(results):
     from gtsfm_amd.runtime.pipeline import FrontEndPipeline
 
     return FrontEndPipeline.matches_to_numpy(results)
+
+
+# bytes per dumped array; together under 64 MB. An array larger than its share is written as a fixed, seeded sample of its rows.
+# (the headline's 1000 pairs x 5000 keypoints of matches0 / matching_scores0 fit whole)
+DUMP_BUDGET = {"keypoint_counts": 500_000, "keypoints": 3_000_000, "keypoint_scores": 1_500_000, "descriptors": 14_000_000, "pairs": 500_000,
+               "matches0": 20_100_000, "matching_scores0": 20_100_000, "scene_match_counts": 500_000, "scene_matches": 2_000_000}
+
+
+def dump_outputs(out_dir: str, feats, res, gathered) -> dict:
+    """Write the last timed step's outputs as float32 .npy files: the feature table (keypoints, scores and descriptors; rows past an
+    image's count zeroed), and per pair in pair order its matches0 / matching_scores0 (image i's side, -1 = unmatched); in scene mode also
+    the gathered (K,2) match lists in sorted pair order. Returns name -> shape written."""
+    path = Path(out_dir)
+    path.mkdir(parents=True, exist_ok=True)
+    count = feats["count"].to(torch.int64)
+    valid = torch.arange(feats["xy"].shape[1], device=count.device)[None, :] < count[:, None]
+    arrays = {
+        "keypoint_counts": count,
+        "keypoints": torch.where(valid[..., None], feats["xy"], 0.0),  # (padding rows may hold anything, NaN included)
+        "keypoint_scores": torch.where(valid, feats["scores"], 0.0),
+        "descriptors": torch.where(valid[..., None], feats["descriptors"], 0.0).reshape(-1, feats["descriptors"].shape[-1]),
+    }
+    arrays = {k: v.float().cpu().numpy() for k, v in arrays.items()}
+    if res:
+        pairs, m0, s0 = [], [], []
+        for chunk in res:
+            m, s = chunk["matches"].cpu().numpy(), chunk["mscores"].cpu().numpy()
+            row = 0
+            for pair, a, b in zip(chunk["pairs"], chunk["n0"], chunk["n1"]):
+                pairs.append(pair)
+                m0.append(m[row : row + a])
+                s0.append(s[row : row + a])
+                row += a + b
+        arrays.update(pairs=np.asarray(pairs, dtype=np.float32).reshape(-1, 2), matches0=np.concatenate(m0).astype(np.float32),
+                      matching_scores0=np.concatenate(s0).astype(np.float32))
+    if gathered is not None:
+        order = sorted(gathered)
+        arrays["scene_match_counts"] = np.asarray([len(gathered[p]) for p in order], dtype=np.float32)
+        arrays["scene_matches"] = np.concatenate([np.asarray(gathered[p], dtype=np.float32).reshape(-1, 2) for p in order] or [np.zeros((0, 2), np.float32)])
+    written = {}
+    for name, arr in arrays.items():
+        row_bytes = max(1, arr[:1].nbytes) if arr.ndim > 1 else arr.itemsize
+        cap = max(1, DUMP_BUDGET[name] // row_bytes)
+        if arr.shape[0] > cap:
+            arr = arr[np.sort(np.random.default_rng(0).choice(arr.shape[0], cap, replace=False))]
+        np.save(path / f"{name}.npy", np.ascontiguousarray(arr, dtype=np.float32))
+        written[name] = list(arr.shape)
+    return written
 
 
 
@@ -864,6 +925,8 @@ def main() -> None:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     ms_per_step = elapsed / args.steps * 1e3
+    if args.dump_outputs and rank == 0:  # before any --full leg reuses the pipeline's buffers
+        dump_outputs(args.dump_outputs, feats, res, gathered)
     detect_only = not have_matcher
     if scene:
         units_per_step = len(all_pairs)

@@ -208,3 +208,63 @@ def test_the_arithmetic_flag_labels_the_line_and_sets_both_switches():
     # the switches are exported before anything launches (the ranks of a self-launch inherit them)
     src = (REPO / "bench.py").read_text()
     assert src.index('os.environ["GTSFM_ATTENTION_MATH"] = os.environ["GTSFM_GEMM_MATH"] = args.arithmetic') < src.index("relaunch_one_process_per_gpu(args.gpus))")
+
+
+def test_a_plain_run_times_the_headline_only_and_full_adds_the_rest():
+    """A plain run sets up, warms up, times --steps steps and prints the line; the rooflines, the CPU baseline with its parity check and the
+    secondary legs run under --full, where the --no-* switches still take single legs out."""
+    import bench
+
+    args = bench.parse_args(["--steps", "4", "--warmup", "2"])
+    assert (args.steps, args.warmup, args.full) == (4, 2, False) and args.no_roofline and args.no_cpu_baseline and args.no_secondary
+    args = bench.parse_args(["--full"])
+    assert args.full and not (args.no_roofline or args.no_cpu_baseline or args.no_secondary)
+    args = bench.parse_args(["--full", "--no-secondary"])
+    assert args.no_secondary and not (args.no_roofline or args.no_cpu_baseline)
+    p, lines = _run_bench("--plumbing-only", "--images", "5", "--pairs", "8", "--steps", "3", "--warmup", "1")
+    assert p.returncode == 0, p.stderr[-2000:]
+    head = json.loads(lines[-1])
+    assert head["steps"] == 3 and head["ms_per_step"] > 0 and not {"roofline", "cpu_baseline", "parity_check", "secondary_rates"} & set(head)
+    p, lines = _run_bench("--plumbing-only", "--steps", "0")
+    assert p.returncode != 0 and not lines
+
+
+def test_dump_outputs_writes_the_last_step_the_same_every_run(tmp_path):
+    """--dump-outputs DIR: the last timed step's feature table and per-pair matches as float32 .npy files, identical from run to run."""
+    import numpy as np
+
+    for tag in ("a", "b"):
+        p, lines = _run_bench("--plumbing-only", "--images", "5", "--pairs", "8", "--steps", "2", "--warmup", "1", "--dump-outputs", str(tmp_path / tag))
+        assert p.returncode == 0, p.stderr[-2000:]
+    got = {f.name[:-4]: np.load(f) for f in sorted((tmp_path / "a").glob("*.npy"))}
+    assert set(got) == {"keypoint_counts", "keypoints", "keypoint_scores", "descriptors", "pairs", "matches0", "matching_scores0"}
+    for name, arr in got.items():
+        assert arr.dtype == np.float32 and np.array_equal(arr, np.load(tmp_path / "b" / f"{name}.npy")), name
+    counts = got["keypoint_counts"].astype(int)
+    assert got["keypoints"].shape[0] == 5 and got["pairs"].tolist() == [list(q) for q in parallel.exhaustive_pairs(5)[:8]]
+    assert got["matches0"].shape == got["matching_scores0"].shape == (sum(counts[int(i)] for i, _ in got["pairs"]),)
+    assert (got["matches0"] > -1).any() and not got["keypoints"][0, counts[0]:].any()  # rows past an image's count are zero
+
+
+def test_dump_outputs_stays_under_64_mb_with_a_seeded_sample(tmp_path):
+    """Outputs larger than their share of the 64 MB budget are written as the same seeded sample of rows every time."""
+    import numpy as np
+    import torch
+
+    import bench
+
+    n, k, pairs = 20, 1000, 1000
+    g = torch.Generator().manual_seed(0)
+    feats = {"count": torch.full((n,), k, dtype=torch.int32), "xy": torch.rand((n, k, 2), generator=g), "scores": torch.rand((n, k), generator=g),
+             "descriptors": torch.rand((n, k, 256), generator=g)}
+    chunk = {"pairs": [(0, 1)] * pairs, "n0": [5200] * pairs, "n1": [1] * pairs}
+    chunk["matches"] = torch.arange(5201 * pairs, dtype=torch.int32) % 977
+    chunk["mscores"] = chunk["matches"].float() / 977
+    shapes = [bench.dump_outputs(str(tmp_path / tag), feats, [chunk], None) for tag in ("a", "b")]
+    assert shapes[0] == shapes[1] and shapes[0]["descriptors"][0] < n * k and shapes[0]["matches0"][0] < 5200 * pairs
+    assert shapes[0]["keypoints"] == [n, k, 2]
+    assert sum(f.stat().st_size for f in (tmp_path / "a").glob("*.npy")) <= 64e6
+    for name in shapes[0]:
+        assert np.array_equal(np.load(tmp_path / "a" / f"{name}.npy"), np.load(tmp_path / "b" / f"{name}.npy"))
+    m0, s0 = np.load(tmp_path / "a" / "matches0.npy"), np.load(tmp_path / "a" / "matching_scores0.npy")
+    np.testing.assert_array_equal(s0, m0 / 977)  # one sample of rows for the indices and their scores

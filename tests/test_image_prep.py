@@ -58,20 +58,36 @@ def test_sizing_rule_reproduces_the_references_known_answers():
 REFERENCE = __import__("pathlib").Path(__import__("os").environ.get("GTSFM_REFERENCE", "/root/reference"))
 
 
-@pytest.mark.skipif(not (REFERENCE / "gtsfm" / "utils" / "images.py").exists(), reason="the reference tree is only mounted in the build container")
 def test_sizing_rule_equals_the_reference_function_run_live():
-    """``gtsfm/utils/images.py:189-220`` itself (imported from /root/reference in a subprocess, the absent third-party packages replaced by inert
-    stand-ins as in oracle/validate_wrappers_against_reference.py; the function is pure arithmetic) over 400 seeded (height, width, max_resolution)
-    triples: the same target size as the oracle's and the product's rule, every time."""
+    """``gtsfm/utils/images.py:189-220`` itself over 400 seeded (height, width, max_resolution) triples: the same target size as the oracle's and
+    the product's rule, every time. The reference's answers are recorded in ``tests/golden/reference_downsampling_sizes.json``; where the
+    reference tree is mounted the function also runs live (imported in a subprocess, the absent third-party packages replaced by inert
+    stand-ins as in oracle/validate_wrappers_against_reference.py; the function is pure arithmetic) and must give the recorded answers."""
+    import json
+
+    from conftest import GOLDEN
+    from gtsfm_amd.runtime.image_prep import downsampled_size
+
+    rng = np.random.default_rng(17)
+    cases = [(int(h), int(w), int(r)) for h, w, r in zip(rng.integers(40, 4000, 400), rng.integers(40, 4000, 400), rng.integers(32, 2000, 400))]
+    recorded = [tuple(v) for v in json.loads((GOLDEN / "reference_downsampling_sizes.json").read_text())]
+    assert len(recorded) == len(cases)
+    if not (REFERENCE / "gtsfm" / "utils" / "images.py").exists():
+        ref = recorded
+    else:
+        ref = _reference_sizes_run_live(cases)
+        assert ref == recorded
+    assert ref == [ipo.downsampled_size(*c) for c in cases] == [downsampled_size(*c) for c in cases]
+    assert sum(1 for c, r in zip(cases, ref) if r != c[:2]) > 100  # the sweep does exercise the downsizing branch
+
+
+def _reference_sizes_run_live(cases):
     import json
     import subprocess
     import sys
 
     from conftest import REPO
-    from gtsfm_amd.runtime.image_prep import downsampled_size
 
-    rng = np.random.default_rng(17)
-    cases = [(int(h), int(w), int(r)) for h, w, r in zip(rng.integers(40, 4000, 400), rng.integers(40, 4000, 400), rng.integers(32, 2000, 400))]
     code = (
         "import json, sys\n"
         f"sys.path.insert(0, {str(REPO / 'oracle')!r}); sys.path.insert(0, {str(REPO)!r})\n"
@@ -84,9 +100,7 @@ def test_sizing_rule_equals_the_reference_function_run_live():
     )
     run = subprocess.run([sys.executable, "-c", code], input=json.dumps(cases), capture_output=True, text=True, timeout=300)
     assert run.returncode == 0, run.stderr[-2000:]
-    ref = [tuple(v) for v in json.loads(run.stdout.strip().splitlines()[-1])]
-    assert ref == [ipo.downsampled_size(*c) for c in cases] == [downsampled_size(*c) for c in cases]
-    assert sum(1 for c, r in zip(cases, ref) if r != c[:2]) > 100  # the sweep does exercise the downsizing branch
+    return [tuple(v) for v in json.loads(run.stdout.strip().splitlines()[-1])]
 
 
 @pytest.mark.parametrize("h,w,nh,nw", [(300, 200, 120, 80), (484, 324, 283, 190), (97, 131, 64, 64), (64, 64, 200, 150)])

@@ -14,9 +14,9 @@ GTSFM_ATTENTION_MATH=bf16x3 GTSFM_GEMM_MATH=bf16x3 python -m pytest tests/test_m
 GTSFM_ATTENTION_MATH=f16x2 GTSFM_GEMM_MATH=f16x2 python -m pytest tests/test_matchers_gpu.py tests/test_lightglue_hf_golden_gpu.py tests/test_lightglue_fp64_arbiter_gpu.py \
     tests/test_config1_lund_door_gpu.py tests/test_reference_contract_gpu.py tests/test_superpoint_gpu.py tests/test_attention_bf16x3_gpu.py -m gpu -q -p no:cacheprovider 2>&1 | tail -6 > $OUT/gpu_tests_f16x2_both_switches.txt
 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.txt 2>&1
-( time python bench.py --gpus 1 --steps 20 --warmup 5 ) > $OUT/bench_default.log 2>&1
+( time python bench.py --gpus 1 --steps 20 --warmup 5 --full ) > $OUT/bench_default.log 2>&1
 cp gpurun_out/bench_details.json $OUT/bench_details.json
-python bench.py --mode scene --steps 1 --warmup 1 --no-secondary --no-cpu-baseline --dump-matches 1 --details-file $OUT/scene_details.json > $OUT/bench_scene_config4_cap5000.log 2>&1
+python bench.py --full --mode scene --steps 1 --warmup 1 --no-secondary --no-cpu-baseline --dump-matches 1 --details-file $OUT/scene_details.json > $OUT/bench_scene_config4_cap5000.log 2>&1
 GTSFM_BENCH_FORCE_DIST=1 MASTER_ADDR=127.0.0.1 MASTER_PORT=29533 python bench.py --mode scene --steps 1 --warmup 1 --no-secondary --no-cpu-baseline --no-roofline --dump-matches 1 \
     --details-file $OUT/scene_rccl_details.json > $OUT/bench_scene_config4_cap5000_rccl_one_rank.log 2>&1
 SCALE_SELFCHECK_OUT=$OUT/scale_selfcheck bash tools/scale_selfcheck.sh 1 > $OUT/scale_selfcheck_n1.txt 2>&1

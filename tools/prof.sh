@@ -2,14 +2,15 @@
 # Profiling recipe (GPU box): kernel trace + stats of the default bench, then separate PMC passes (HBM traffic) on a
 # short SuperPoint-only run. Outputs land in gpurun_out/prof_<tag>/.
 set -u
+export BENCH="$(cd "$(dirname "$0")/.." && pwd)/bench.py"  # the benchmark of this tree
 TAG=${1:-r01}
 OUT=$GRAFT_REPO_ROOT/gpurun_out/prof_$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/full -o full -- python $GRAFT_REPO_ROOT/bench.py --steps 2 --warmup 1 --no-cpu-baseline > $OUT/full.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/full -o full -- python $BENCH --full --steps 2 --warmup 1 --no-cpu-baseline > $OUT/full.log 2>&1
 rm -f $OUT/full/*kernel_trace.csv
 cat > /tmp/pmc_workload.sh <<'SH'
-python $GRAFT_REPO_ROOT/bench.py --matcher none --images 4 --steps 1 --warmup 1 --no-cpu-baseline
+python $BENCH --full --matcher none --images 4 --steps 1 --warmup 1 --no-cpu-baseline
 python $GRAFT_REPO_ROOT/tools/gpu_time_lg.py
 SH
 for C in FETCH_SIZE WRITE_SIZE; do

@@ -2,11 +2,12 @@
 # Round-2 profiles (GPU box): kernel-trace stats of the two bench workloads (one stream, eager launches, so that per-kernel
 # durations are the isolated ones) and separate PMC passes (FETCH_SIZE / WRITE_SIZE) of the hot kernels at workload shape.
 set -u
+export BENCH="$(cd "$(dirname "$0")/.." && pwd)/bench.py"  # the benchmark of this tree
 OUT=$GRAFT_REPO_ROOT/gpurun_out/prof_r02
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/lg -o lg -- python $GRAFT_REPO_ROOT/bench.py --steps 1 --warmup 1 --streams 1 --graphs 0 --no-cpu-baseline --no-secondary > $OUT/lg.log 2>&1
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/sg -o sg -- python $GRAFT_REPO_ROOT/bench.py --matcher superglue --sinkhorn 100 --pairs 256 --steps 1 --warmup 1 --streams 1 --graphs 0 --no-cpu-baseline --no-secondary > $OUT/sg.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/lg -o lg -- python $BENCH --full --steps 1 --warmup 1 --streams 1 --graphs 0 --no-cpu-baseline --no-secondary > $OUT/lg.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/sg -o sg -- python $BENCH --full --matcher superglue --sinkhorn 100 --pairs 256 --steps 1 --warmup 1 --streams 1 --graphs 0 --no-cpu-baseline --no-secondary > $OUT/sg.log 2>&1
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/vf -o vf -- python $GRAFT_REPO_ROOT/tools/prof_verifier.py > $OUT/vf.log 2>&1
 find $OUT -name "*kernel_trace.csv" -delete
 for W in "attention" "gemm 256 768" "gemm 512 512" "gemm 512 256" "sinkhorn"; do
