@@ -26,18 +26,19 @@ from gtsfm_amd.frontend.detector_descriptor.superpoint import SuperPointDetector
 from gtsfm_amd.frontend.matcher.lightglue_matcher import LightGlueMatcher
 from gtsfm_amd.frontend.matcher.matcher_base import MatcherBase
 from gtsfm_amd.frontend.matcher.superglue_matcher import DEFAULT_MATCH_THRESHOLD, SuperGlueMatcher
+from gtsfm_amd.frontend.matcher.twoway_matcher import TwoWayMatcher
 
 
 class BatchedDetDescCorrespondenceGenerator(CorrespondenceGeneratorBase):
-    """Batched, GPU-resident SuperPoint + {SuperGlue, LightGlue} correspondence generation."""
+    """Batched, GPU-resident SuperPoint + {SuperGlue, LightGlue, TwoWay} correspondence generation."""
 
     def __init__(
         self, matcher: MatcherBase, detector_descriptor: SuperPointDetectorDescriptor, image_batch: int = 16, pair_batch: int = 32
     ) -> None:
         if not isinstance(detector_descriptor, SuperPointDetectorDescriptor):
             raise TypeError("BatchedDetDescCorrespondenceGenerator needs gtsfm_amd's SuperPointDetectorDescriptor")
-        if not isinstance(matcher, (SuperGlueMatcher, LightGlueMatcher)):
-            raise TypeError("BatchedDetDescCorrespondenceGenerator needs gtsfm_amd's SuperGlueMatcher or LightGlueMatcher")
+        if not isinstance(matcher, (SuperGlueMatcher, LightGlueMatcher, TwoWayMatcher)):
+            raise TypeError("BatchedDetDescCorrespondenceGenerator needs gtsfm_amd's SuperGlueMatcher, LightGlueMatcher or TwoWayMatcher")
         self._detector_descriptor = detector_descriptor
         self._matcher = matcher
         self._image_batch = image_batch
@@ -76,6 +77,11 @@ class BatchedDetDescCorrespondenceGenerator(CorrespondenceGeneratorBase):
 
         if not isinstance(verifier, Ransac):
             raise TypeError("generate_correspondences_and_verify needs gtsfm_amd's Ransac verifier")
+        if isinstance(self._matcher, TwoWayMatcher):
+            # the device verifier reads each edge's putative rows in i1 order straight from the matcher's output; TwoWayMatcher's are
+            # sorted by distance
+            raise TypeError("generate_correspondences_and_verify does not support TwoWayMatcher: call generate_correspondences and "
+                            "verify each edge with the verifier plugin")
         keypoints_list, putative, state = self._detect_and_match(client, images, visibility_graph)
         params = [pinhole_parameters(c) for c in camera_intrinsics]
         use_intrinsics = bool(verifier._use_intrinsics_in_verification)
@@ -118,6 +124,16 @@ class BatchedDetDescCorrespondenceGenerator(CorrespondenceGeneratorBase):
         keypoints_list = keypoints_from_table(feats, counts)
 
         pairs = [(int(i1), int(i2)) for (i1, i2) in visibility_graph]
+        if isinstance(matcher, TwoWayMatcher):  # every edge from the resident descriptor table, pair_batch edges per launch
+            from gtsfm_amd.frontend.matcher.twoway_matcher import _metric
+            from gtsfm_amd.runtime.twoway_engine import EUCLIDEAN
+
+            metric = _metric(matcher._distance_type)
+            if metric != EUCLIDEAN:
+                raise TypeError("TwoWayMatcher on SuperPoint's float32 descriptors needs MatchingDistanceType.EUCLIDEAN")
+            result = matcher._model.match_table(feats["descriptors"], counts, pairs, metric, matcher._ratio_test_threshold,
+                                                pair_batch=self._pair_batch)
+            return keypoints_list, result, {"feats": feats}
         todo, empty = split_empty_pairs(pairs, counts)  # superglue.py:233-240 early-out
         dtype, kwargs = match_output_convention(matcher)
         results = pipe.match(feats, todo, shapes, counts=counts, **kwargs) if todo else []

@@ -168,6 +168,12 @@ SIGNATURES = {
         C.c_int,
         [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p],
     ),
+    "gtsfm_twoway_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "gtsfm_twoway_match": (
+        C.c_int,
+        [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_double, C.c_void_p, C.c_size_t, C.c_void_p,
+         C.c_void_p, C.c_void_p],
+    ),
 }
 
 

@@ -392,6 +392,25 @@ int gtsfm_verify_compact_matches(const int32_t* matches_dev, const long long* ro
                                  const long long* match_off_dev, int num_pairs, int32_t* match_idx_dev, int32_t* match_count_dev,
                                  void* stream);
 
+/* ---- TwoWayMatcher: brute-force mutual nearest neighbour with an optional ratio test ----
+ *                                  replaces gtsfm/frontend/matcher/twoway_matcher.py:40-147 (cv.BFMatcher match / knnMatch(k=2),
+ *                                  run 1->2 and 2->1, then the mutual check).
+ * desc_dev: one descriptor table, row r at desc_dev + r * row_stride elements; float32 (desc_is_u8 = 0) or uint8 (1).
+ * metric: 1 = HAMMING (popcount of a XOR b over the bytes; uint8 only), 2 = EUCLIDEAN (sqrtf of the sum of squares).
+ * pairs_host [npairs][4] int32 = (first row of side 1, n1, first row of side 2, n2); n1, n2 >= 1; rows 0 .. max(first + n) - 1
+ * of the table must be readable. Side 1 row i's nearest side-2 row j (ties -> lower j) is kept iff, with use_ratio,
+ * (double)d1st <= ratio * (double)d2nd (second entry of the top-2, duplicates counted), and side 2 row j's nearest side-1 row,
+ * under the same test, is i. Outputs, pair p's block starting at the sum of the n1 of the pairs before it:
+ * matches0_dev [sum n1] int32 = j or -1; dist0_dev [sum n1] float32 = the distance of row i to its nearest side-2 row.
+ * The product is computed once per pair in exact fp32 (v_mfma_f32_32x32x2_f32) and never stored; integer descriptors with
+ * max|a|^2 + max|b|^2 < 2^24 give the reference's distances bit for bit. At most 65535 pairs per call; partial offsets are 64-bit, so
+ * the workspace (gtsfm_twoway_workspace_bytes, ~3.3 MB per 5000 x 5000 pair) is the only bound. Copies the batch descriptor into the workspace and
+ * synchronises `stream` once. */
+size_t gtsfm_twoway_workspace_bytes(int desc_is_u8, int metric, int dim, int row_stride, int npairs, const int32_t* pairs_host);
+int gtsfm_twoway_match(const void* desc_dev, int desc_is_u8, int metric, int dim, int row_stride, int npairs, const int32_t* pairs_host,
+                       int use_ratio, double ratio, void* workspace_dev, size_t workspace_bytes, int32_t* matches0_dev, float* dist0_dev,
+                       void* stream);
+
 #ifdef __cplusplus
 }
 #endif
