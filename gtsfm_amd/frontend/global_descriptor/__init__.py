@@ -1,0 +1,23 @@
+"""Global image descriptors (``gtsfm/frontend/global_descriptor``): short-name exports, loaded lazily like the reference's package
+(``_target_: gtsfm_amd.frontend.global_descriptor.NetVLAD``)."""
+
+import importlib
+
+__all__ = ["NetVLAD", "NetVLADGlobalDescriptor"]
+
+_MOD_MAP = {
+    "NetVLAD": ("gtsfm_amd.frontend.global_descriptor.netvlad_global_descriptor", "NetVLADGlobalDescriptor"),
+    "NetVLADGlobalDescriptor": ("gtsfm_amd.frontend.global_descriptor.netvlad_global_descriptor", "NetVLADGlobalDescriptor"),
+}
+
+
+def __getattr__(name: str):
+    try:
+        module_name, class_name = _MOD_MAP[name]
+    except KeyError as e:
+        raise AttributeError(name) from e
+    return getattr(importlib.import_module(module_name), class_name)
+
+
+def __dir__():
+    return sorted(list(globals().keys()) + __all__)

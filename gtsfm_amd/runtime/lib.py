@@ -174,6 +174,22 @@ SIGNATURES = {
         [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_double, C.c_void_p, C.c_size_t, C.c_void_p,
          C.c_void_p, C.c_void_p],
     ),
+    "gtsfm_netvlad_packed_weight_floats": (C.c_size_t, [C.c_int]),
+    "gtsfm_netvlad_pack_weights": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.c_void_p]),
+    "gtsfm_netvlad_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "gtsfm_netvlad_forward": (
+        C.c_int,
+        [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p],
+    ),
+    "gtsfm_netvlad_stage": (
+        C.c_int,
+        [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p],
+    ),
+    "gtsfm_retrieval_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "gtsfm_retrieval_topk": (
+        C.c_int,
+        [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p],
+    ),
 }
 
 

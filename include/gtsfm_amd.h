@@ -411,6 +411,51 @@ int gtsfm_twoway_match(const void* desc_dev, int desc_is_u8, int metric, int dim
                        int use_ratio, double ratio, void* workspace_dev, size_t workspace_bytes, int32_t* matches0_dev, float* dist0_dev,
                        void* stream);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * NetVLAD global descriptor and similarity retrieval
+ *   NV = thirdparty/hloc/netvlad.py, SR = gtsfm/retriever/similarity_retriever.py
+ * ---------------------------------------------------------------------------------------------------------- */
+
+/* Packed NetVLAD weights (floats) and the packer. tensors_host, torch layouts, in this order: the 13 backbone convolutions
+ * conv1_1 .. conv5_3 as (weight [out][in][3][3], bias [out]) pairs (26 tensors), score_proj.weight [64][512], centers [512][64],
+ * mean [3]; with whiten also whiten.weight [4096][32768] and whiten.bias [4096] (31 tensors). The whitening matrix is 512 MB.
+ *                                                                                                        replaces NV:103-163 */
+size_t gtsfm_netvlad_packed_weight_floats(int whiten);
+int gtsfm_netvlad_pack_weights(const float* const* tensors_host, int whiten, float* packed_host);
+
+/* Bytes of device workspace a forward / stage call needs for `batch` images of height x width (0 for an invalid shape:
+ * batch >= 1, height, width >= 16). Indexing is 64-bit throughout; the workspace (~320 bytes per pixel) is the only bound. */
+size_t gtsfm_netvlad_workspace_bytes(int batch, int height, int width);
+
+/* NetVLAD.forward for a batch of equally-sized RGB images, exact fp32.                                  replaces NV:166-202
+ * layout 0: image_dev [batch][3][height][width] float32 in [0, 1] (the loader's batch transform output); the reference's
+ *           preprocessing clamp(x * 255, 0, 255) - mean is applied as it does.
+ * layout 1: image_dev [batch][height][width][3] uint8; equals layout 0 fed with float(u8) / 255, bit for bit.
+ * whiten: 1 -> out_dev [batch][4096] (packed weights must include the whitening), 0 -> out_dev [batch][32768].
+ * range_flag_dev (optional, int32, not cleared here): bit 0 is set when a layout-0 value is NaN or outside [-1e-6, 1 + 1e-6]
+ * (the reference's assert, NV:177); the caller reads it after the call. Per image, the result does not depend on the batch. */
+int gtsfm_netvlad_forward(const float* packed_weights_dev, const void* image_dev, int layout, int batch, int height, int width, int whiten,
+                          float* out_dev, int32_t* range_flag_dev, void* workspace_dev, size_t workspace_bytes, void* stream);
+
+/* The stages of gtsfm_netvlad_forward (same kernels), for stage-wise tests. stage 0: relu(conv1_1(preprocessed image)),
+ * [batch][height][width][64] NHWC; 1: conv5_3 (no ReLU), [batch][height / 16][width / 16][512] NHWC (floor at every pool);
+ * 2: the NetVLAD layer's output before whitening, [batch][32768], index d * 64 + k. */
+int gtsfm_netvlad_stage(const float* packed_weights_dev, const void* image_dev, int layout, int batch, int height, int width, int stage, float* out_dev,
+                        void* workspace_dev, size_t workspace_bytes, void* stream);
+
+/* Bytes of device workspace gtsfm_retrieval_topk needs for n descriptors of dimension d (with_sim_out: whether the caller
+ * passes sim_out_dev; without it the workspace holds the n x n product). */
+size_t gtsfm_retrieval_workspace_bytes(int n, int d, int with_sim_out);
+
+/* Similarity retrieval: S = D D^T (exact fp32, v_mfma_f32_32x32x2_f32; only row strips from their diagonal block on are
+ * computed), then per row i the kk = min(k, n) best columns j > i with S[i][j] >= min_score (float compare; pass -INFINITY for
+ * no threshold) and S[i][j] finite, in descending score order; EQUAL SCORES ARE BROKEN BY THE LOWER j (torch.topk makes no
+ * promise). idx_out_dev / score_out_dev [n][kk]: column index or -1 (score -inf) for an empty rank.   replaces SR:98-245
+ * sim_out_dev (optional, [n][n]): S in the reference's block layout: (i, j) holds D_i . D_j iff j / blocksize >= i / blocksize,
+ * else 0 (n <= 65535). */
+int gtsfm_retrieval_topk(const float* desc_dev, int n, int d, int k, float min_score, int blocksize, int32_t* idx_out_dev, float* score_out_dev,
+                         float* sim_out_dev, void* workspace_dev, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
