@@ -14,8 +14,9 @@
 //   6. nv_vlad_kernel     : V[d][k] = sum_n a[k][n] (x[d][n] - c[d][k]) in the residual form (netvlad.py:67-68) without the
 //                           (B, 512, 64, HW) difference tensor: 64-pixel chunks summed in order, chunk sums added in order.
 //   7. nv_vlad_norm_kernel: intra-normalisation per cluster, flatten at d * 64 + k, global normalisation (netvlad.py:69-72).
-//   8. nv_whiten_kernel   : whitening 32768 -> 4096 as a split-K product (16 slices of 2048, four images per workgroup, a wave
-//                           per output column); nv_whiten_finish_kernel sums the slices in order, adds the bias and normalises.
+//   8. sk_linear_kernel   : whitening 32768 -> 4096 as a split-K product (splitk_linear.h, shared with MegaLoc's output projection: 16
+//                           slices of 2048, four images per workgroup, a wave per output column); sk_finish_kernel sums the slices in
+//                           order, adds the bias and normalises.
 // Every image's values follow the same operation order whatever the batch, so a batch equals its images one at a time, bit for bit.
 //
 // Retrieval: S = D D^T through ONE batched launch of the LDS-DMA GEMM over row strips of 1024 (each strip from its diagonal block
@@ -31,6 +32,7 @@
 #include "conv_kernels.h"
 #include "gemm_batch.h"
 #include "gemm_kernels.h"
+#include "splitk_linear.h"
 
 #define NV_LAYERS 13
 #define NV_D 512
@@ -39,7 +41,6 @@
 #define NV_WHITE 4096
 #define NV_WSLICE 2048                 // depth of one whitening slice
 #define NV_WSPLIT (NV_VLAD / NV_WSLICE)  // 16
-#define NV_WIMG 4                      // images per whitening workgroup
 #define NV_C1_T 16                     // conv1_1 output tile: 16 x 16 pixels
 #define RT_STRIP 1024                  // rows per retrieval GEMM problem
 
@@ -253,56 +254,6 @@ __global__ __launch_bounds__(256) void nv_vlad_norm_kernel(const float* __restri
     for (int idx = tid; idx < NV_VLAD; idx += 256) ob[idx] = ob[idx] / gn;
 }
 
-// part[s][b][n] = sum over slice s of W[n][k] vlad[b][k]. grid (4096 / 64, 16, ceil(B / 4)); a wave walks 16 columns, a lane
-// holds 32 depths of four images in registers and reads W[n] as float4 (one 1 KB row piece per wave instruction).
-__global__ __launch_bounds__(256) void nv_whiten_kernel(const float* __restrict__ vlad, const float* __restrict__ w, int B, float* __restrict__ part) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int s = blockIdx.y, b0 = blockIdx.z * NV_WIMG;
-    const size_t k0 = (size_t)s * NV_WSLICE + 4 * lane;
-    f32x4 xr[NV_WIMG][8];
-#pragma unroll
-    for (int bi = 0; bi < NV_WIMG; ++bi)
-#pragma unroll
-        for (int i = 0; i < 8; ++i)
-            xr[bi][i] = (b0 + bi < B) ? *reinterpret_cast<const f32x4*>(vlad + (size_t)(b0 + bi) * NV_VLAD + k0 + 256 * i) : f32x4{0.f, 0.f, 0.f, 0.f};
-    for (int col = 0; col < 16; ++col) {
-        const int n = blockIdx.x * 64 + wave * 16 + col;
-        const float* wr = w + (size_t)n * NV_VLAD + k0;
-        f32x4 wv[8];
-#pragma unroll
-        for (int i = 0; i < 8; ++i) wv[i] = *reinterpret_cast<const f32x4*>(wr + 256 * i);
-#pragma unroll
-        for (int bi = 0; bi < NV_WIMG; ++bi) {
-            float acc = 0.f;
-#pragma unroll
-            for (int i = 0; i < 8; ++i)
-#pragma unroll
-                for (int e = 0; e < 4; ++e) acc = fmaf(wv[i][e], xr[bi][i][e], acc);
-            acc = wave_sum(acc);
-            if (lane == 0 && b0 + bi < B) part[((size_t)s * B + b0 + bi) * NV_WHITE + n] = acc;
-        }
-    }
-}
-
-// y = (sum of the 16 slices in order) + bias, then y / max(||y||, 1e-12) (one workgroup per image).
-__global__ __launch_bounds__(256) void nv_whiten_finish_kernel(const float* __restrict__ part, const float* __restrict__ bias, int B, float* __restrict__ out) {
-    __shared__ float red[4];
-    const int b = blockIdx.x, tid = threadIdx.x;
-    float y[NV_WHITE / 256];
-    float g = 0.f;
-#pragma unroll
-    for (int i = 0; i < NV_WHITE / 256; ++i) {
-        const int n = tid + 256 * i;
-        float acc = 0.f;
-        for (int s = 0; s < NV_WSPLIT; ++s) acc += part[((size_t)s * B + b) * NV_WHITE + n];
-        y[i] = acc + bias[n];
-        g = fmaf(y[i], y[i], g);
-    }
-    const float gn = fmaxf(sqrtf(block_sum256(g, red)), 1e-12f);
-#pragma unroll
-    for (int i = 0; i < NV_WHITE / 256; ++i) out[(size_t)b * NV_WHITE + tid + 256 * i] = y[i] / gn;
-}
-
 // ------------------------------------------------------------------------------------------------------------------------------
 // Retrieval
 // ------------------------------------------------------------------------------------------------------------------------------
@@ -451,10 +402,11 @@ int nv_run(const float* wts, const void* image, int layout, int B, int H, int W,
     GTSFM_CHECK_LAUNCH("nv_vlad_norm_kernel");
     if (stage == 2 || !whiten) return GTSFM_OK;
     float* part = reinterpret_cast<float*>(base + s.part);
-    hipLaunchKernelGGL(nv_whiten_kernel, dim3(NV_WHITE / 64, NV_WSPLIT, ceil_div(B, NV_WIMG)), dim3(256), 0, st, vlad, wts + L.ww, B, part);
-    GTSFM_CHECK_LAUNCH("nv_whiten_kernel");
-    hipLaunchKernelGGL(nv_whiten_finish_kernel, dim3(B), dim3(256), 0, st, part, wts + L.wb, B, out);
-    GTSFM_CHECK_LAUNCH("nv_whiten_finish_kernel");
+    hipLaunchKernelGGL(sk_linear_kernel<NV_WSLICE / 256>, dim3(NV_WHITE / 64, NV_WSPLIT, ceil_div(B, SK_IMG)), dim3(256), 0, st, vlad, wts + L.ww, NV_VLAD,
+                       NV_WHITE, B, part);
+    GTSFM_CHECK_LAUNCH("sk_linear_kernel");
+    hipLaunchKernelGGL((sk_finish_kernel<NV_WSPLIT, 256>), dim3(B), dim3(256), 0, st, part, wts + L.wb, NV_WHITE, B, out);
+    GTSFM_CHECK_LAUNCH("sk_finish_kernel");
     return GTSFM_OK;
 }
 

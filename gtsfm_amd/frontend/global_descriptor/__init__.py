@@ -3,9 +3,11 @@
 
 import importlib
 
-__all__ = ["NetVLAD", "NetVLADGlobalDescriptor"]
+__all__ = ["MegaLoc", "MegaLocGlobalDescriptor", "NetVLAD", "NetVLADGlobalDescriptor"]
 
 _MOD_MAP = {
+    "MegaLoc": ("gtsfm_amd.frontend.global_descriptor.megaloc_global_descriptor", "MegaLocGlobalDescriptor"),
+    "MegaLocGlobalDescriptor": ("gtsfm_amd.frontend.global_descriptor.megaloc_global_descriptor", "MegaLocGlobalDescriptor"),
     "NetVLAD": ("gtsfm_amd.frontend.global_descriptor.netvlad_global_descriptor", "NetVLADGlobalDescriptor"),
     "NetVLADGlobalDescriptor": ("gtsfm_amd.frontend.global_descriptor.netvlad_global_descriptor", "NetVLADGlobalDescriptor"),
 }

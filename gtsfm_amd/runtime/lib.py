@@ -190,6 +190,19 @@ SIGNATURES = {
         C.c_int,
         [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p],
     ),
+    "gtsfm_megaloc_packed_weight_floats": (C.c_size_t, [C.c_int, C.c_int]),
+    "gtsfm_megaloc_pack_weights": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_void_p]),
+    "gtsfm_megaloc_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    "gtsfm_megaloc_forward": (
+        C.c_int,
+        [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
+         C.c_void_p],
+    ),
+    "gtsfm_megaloc_stage": (
+        C.c_int,
+        [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t,
+         C.c_void_p],
+    ),
 }
 
 

@@ -456,6 +456,48 @@ size_t gtsfm_retrieval_workspace_bytes(int n, int d, int with_sim_out);
 int gtsfm_retrieval_topk(const float* desc_dev, int n, int d, int k, float min_score, int blocksize, int32_t* idx_out_dev, float* score_out_dev,
                          float* sim_out_dev, void* workspace_dev, size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * MegaLoc global descriptor (DINOv2 ViT-B/14 + SALAD + linear)
+ *   ML = thirdparty/megaloc/megaloc.py, MG = gtsfm/frontend/global_descriptor/megaloc_global_descriptor.py,
+ *   HF = transformers.models.dinov2.modeling_dinov2 (the backbone's pin: torch.hub's DINOv2 is not in the reference checkout)
+ * Fixed: hidden size 768, 12 heads, patch 14, MLP ratio 4, 64 clusters x 256 channels, token part 256, SALAD MLP width 512.
+ * From the weights: depth (transformer blocks; 12 in the published model) and feat_dim (8448; a multiple of 64).
+ * ---------------------------------------------------------------------------------------------------------- */
+
+/* Packed MegaLoc weights (floats) and the packer (0 for an invalid depth / feat_dim). tensors_host, torch layouts, 20 + 14 * depth
+ * tensors in this order: patch_embed.proj.weight [768][3][14][14], its bias, cls_token [768]; per block norm1.weight, norm1.bias,
+ * attn.qkv.weight [2304][768] (rows q | k | v), attn.qkv.bias, attn.proj.weight, attn.proj.bias, ls1.gamma, norm2.weight, norm2.bias,
+ * mlp.fc1.weight [3072][768], mlp.fc1.bias, mlp.fc2.weight [768][3072], mlp.fc2.bias, ls2.gamma; norm.weight, norm.bias; SALAD
+ * token_features.{0,2} (weight, bias) x 2, cluster_features.{0,3} x 2, score.{0,3} x 2 (1 x 1 convolutions as [out][in]), dust_bin [1];
+ * linear.weight [feat_dim][16640], linear.bias. The LayerScale vectors are folded into attn.proj and mlp.fc2 (weight rows and
+ * bias times gamma, in float32). The position table is not packed: it depends on the image size (see gtsfm_megaloc_forward).
+ *                                                                                                replaces ML:19-46, 85-93, 233-263 */
+size_t gtsfm_megaloc_packed_weight_floats(int depth, int feat_dim);
+int gtsfm_megaloc_pack_weights(const float* const* tensors_host, int depth, int feat_dim, float* packed_host);
+
+/* Bytes of device workspace a forward / stage call needs (0 for an invalid shape: batch >= 1, height and width multiples of 14,
+ * more than 64 patches). A batch runs in chunks of at most 64 images through one workspace, so the size stops growing there. */
+size_t gtsfm_megaloc_workspace_bytes(int batch, int height, int width, int feat_dim);
+
+/* MegaLocModel.forward for a batch of equally-sized RGB images, exact fp32.                   replaces ML:62-71, 104-120, 144-283 and HF's
+ * Dinov2Embeddings / Dinov2Layer / layernorm.
+ * pos_dev: the position table [1 + n][768] for THIS grid, n = (height / 14) (width / 14): row 0 the class position, rows 1 .. n the
+ *          patch positions interpolated by the caller (HF: bicubic, align_corners = False); weight preparation, not hot path.
+ * layout 0: image_dev [batch][3][height][width] float32, already normalised (MG:52-57: x / 255, ImageNet mean / std).
+ * layout 1: image_dev [batch][3][height][width] uint8; ((float)u8 / 255 - mean[c]) / std[c] is applied while the patches are read:
+ *           equals layout 0 fed with that arithmetic in float32, bit for bit.
+ * out_dev [batch][feat_dim], unit rows. flag_dev (optional, int32, not cleared here): bit 0 is set when a layout-0 value is not finite;
+ * the caller reads it after the call. Height or width not a multiple of 14 (ML:64-67 resizes) and n <= 64 (NaN in ML:170) are refused.
+ * Per image, the result does not depend on the batch. */
+int gtsfm_megaloc_forward(const float* packed_weights_dev, int depth, int feat_dim, const float* pos_dev, const void* image_dev, int layout, int batch,
+                          int height, int width, float* out_dev, int32_t* flag_dev, void* workspace_dev, size_t workspace_bytes, void* stream);
+
+/* The stages of gtsfm_megaloc_forward (same kernels), for stage-wise tests. stage 0: the tokens after patch embedding, class token and
+ * position table, [batch][1 + n][768]; 1: the output of block 0, same shape; 2: the final LayerNorm's tokens (row 0 x_norm_clstoken, rows
+ * 1 .. n x_norm_patchtokens), same shape; 3: the SALAD vector before the linear layer, [batch][16640] (token part, then l * 64 + m). */
+int gtsfm_megaloc_stage(const float* packed_weights_dev, int depth, int feat_dim, const float* pos_dev, const void* image_dev, int layout, int batch, int height,
+                        int width, int stage, float* out_dev, void* workspace_dev, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
