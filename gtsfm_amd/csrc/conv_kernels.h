@@ -21,6 +21,9 @@ struct ConvParams {
 };
 
 int launch_conv3x3(const ConvParams& p, hipStream_t stream);
+// The same convolution with dilation 2 and zero pad 2 (same packed weights; no pool, no fused first layer; Cout, out_stride and
+// out_coff multiples of 4).
+int launch_conv3x3_dil2(const ConvParams& p, hipStream_t stream);
 
 size_t packed_conv3x3_floats(int cin, int cout);
 size_t packed_linear_floats(int k, int n);

@@ -8,6 +8,8 @@
 
 #include <stdlib.h>
 
+#include <atomic>
+
 #include "conv_kernels.h"
 #include "mfma_tiles.h"
 
@@ -255,6 +257,159 @@ int launch_conv3x3(const ConvParams& pin, hipStream_t stream) {
         hipLaunchKernelGGL(conv3x3_mfma_kernel<false>, grid, dim3(256), lds_bytes, stream, p);
     }
     GTSFM_CHECK_LAUNCH("conv3x3_mfma_kernel");
+    return GTSFM_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// conv3x3 with dilation 2, stride 1, zero pad 2, NHWC (D2-Net's conv4_1 .. conv4_3, thirdparty/d2net/lib/model_test.py:34-38).
+// A sibling of conv3x3_mfma_kernel<false> -- same workgroup tile, packed weights (pack_conv3x3_weights does not depend on the
+// dilation), k-step pipeline and pinned issue order -- kept apart so that the dilation-1 code object stays what it was.
+// LDS: (8+4) x (16+4) halo pixels x 64 channels; halo row pitch 20 x 68 + 48 = 1408 = 0 (mod 64 banks) as above; 12 rows = 67,584
+// bytes, two workgroups per CU. A tap's offset is 2 (ky pitch + kx 68).
+// ---------------------------------------------------------------------------------------------------------------
+
+#define CD_DIL 2
+#define CD_HW (CV_TW + 2 * CD_DIL)
+#define CD_HH (CV_TH + 2 * CD_DIL)
+#define CD_HALO_PIX (CD_HH * CD_HW)
+#define CD_ROW_PITCH (CD_HW * MT_LDS_ROW + 48)
+#define CD_HALO_FLOATS (CD_HH * CD_ROW_PITCH)
+static_assert(CD_ROW_PITCH % 64 == 0, "halo row pitch must be a multiple of the 64 LDS banks");
+
+__global__ __launch_bounds__(256, 2) void conv3x3_dil2_mfma_kernel(ConvParams p) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int wm = wave >> 1, wn = wave & 1;
+
+    int bid = blockIdx.x;
+    const int tx = bid % p.tiles_x;
+    bid /= p.tiles_x;
+    const int ty = bid % p.tiles_y;
+    const int b = bid / p.tiles_y;
+    const int x0 = tx * CV_TW, y0 = ty * CV_TH;
+    const int nb = blockIdx.y;
+    const int nchunks = p.Cin >> 6;
+    const int total_steps = nchunks * 72;
+    const float* __restrict__ wp = p.wpack + (size_t)nb * total_steps * MT_PACK_STEP_FLOATS;
+
+    const int j = lane & 31, kh = lane >> 5;
+    const int cout = nb * 64 + wn * 32 + j;
+    const float bias = p.bias[cout];  // bias array is padded to a multiple of 64
+    // Every 64-channel chunk (576 products) is summed from zero in acc0 / acc1 and then added to the running totals, which start at the
+    // bias: chains of 576 and of Cin / 64 terms instead of one of 9 Cin = 4608, whose rounding error grows with its length (measured on
+    // D2-Net's dense map: the single chain sat 1.8e-6 of the map's maximum from the CPU reference, whose own float64 distance is 4e-7).
+    f32x16 acc0, acc1, tot0, tot1;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        tot0[r] = bias;
+        tot1[r] = bias;
+    }
+
+    const int a_base0 = (4 * wm + (j >> 4)) * CD_ROW_PITCH + (j & 15) * MT_LDS_ROW + kh * 4;
+    const int a_base1 = a_base0 + 2 * CD_ROW_PITCH;
+    const float* __restrict__ in_b = p.in + (size_t)b * p.H * p.W * p.in_stride + p.in_coff;
+
+    int kstep = 0;
+    f32x4 bcur = mt_load_b(wp, 0, wn, lane);
+    f32x4 bnxt = mt_load_b(wp, 1, wn, lane);  // total_steps >= 72
+    f32x4 bnx2 = mt_load_b(wp, 2, wn, lane);
+    for (int cc = 0; cc < nchunks; ++cc) {
+        if (cc > 0) __syncthreads();
+        // stage the halo tile of this 64-channel chunk: 240 pixels x 16 float4
+        for (int idx = tid; idx < CD_HALO_PIX * 16; idx += 256) {
+            const int pix = idx >> 4, q = idx & 15;
+            const int gy = y0 - CD_DIL + pix / CD_HW, gx = x0 - CD_DIL + pix % CD_HW;
+            f32x4 v = {0.f, 0.f, 0.f, 0.f};
+            if (gy >= 0 && gy < p.H && gx >= 0 && gx < p.W)
+                v = *reinterpret_cast<const f32x4*>(in_b + ((size_t)gy * p.W + gx) * p.in_stride + cc * 64 + q * 4);
+            *reinterpret_cast<f32x4*>(&lds[(pix / CD_HW) * CD_ROW_PITCH + (pix % CD_HW) * MT_LDS_ROW + q * 4]) = v;
+        }
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            acc0[r] = 0.f;
+            acc1[r] = 0.f;
+        }
+        __syncthreads();
+        for (int tap = 0; tap < 9; ++tap) {
+            const int toff = CD_DIL * ((tap / 3) * CD_ROW_PITCH + (tap % 3) * MT_LDS_ROW);
+            f32x4 a0 = *reinterpret_cast<const f32x4*>(&lds[a_base0 + toff]);
+            f32x4 a1 = *reinterpret_cast<const f32x4*>(&lds[a_base1 + toff]);
+            __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
+#pragma unroll
+            for (int c8 = 0; c8 < 8; ++c8) {
+                const int nxt = (kstep + 3 < total_steps) ? kstep + 3 : total_steps - 1;
+                const f32x4 bnext = mt_load_b(wp, nxt, wn, lane);
+                f32x4 a0n = a0, a1n = a1;
+                if (c8 < 7) {
+                    a0n = *reinterpret_cast<const f32x4*>(&lds[a_base0 + toff + (c8 + 1) * 8]);
+                    a1n = *reinterpret_cast<const f32x4*>(&lds[a_base1 + toff + (c8 + 1) * 8]);
+                }
+                mt_step(acc0, acc1, a0, a1, bcur);
+                bcur = bnxt;
+                bnxt = bnx2;
+                bnx2 = bnext;
+                a0 = a0n, a1 = a1n;
+                ++kstep;
+                __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
+                if (c8 < 7) __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
+                __builtin_amdgcn_sched_group_barrier(0x008, 8, 0);
+            }
+        }
+        tot0 += acc0;
+        tot1 += acc1;
+    }
+
+    // output transposed through LDS as in conv3x3_mfma_kernel (a 32 x 32 scratch tile per wave inside the halo tile)
+    __syncthreads();  // every wave is done with the halo tile
+    float* scr = lds + wave * 1024;
+    float* __restrict__ out_t = p.out + (size_t)b * p.H * p.W * p.out_stride + p.out_coff + nb * 64 + wn * 32;
+    const int tp = lane >> 3, tc = lane & 7;
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            float v = t ? tot1[r] : tot0[r];
+            if (p.relu) v = fmaxf(v, 0.f);
+            scr[mt_acc_row(r, lane) * 32 + j] = v;
+        }
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int row = tp + 8 * i;  // pixel of the wave's 32: tile row 4 wm + 2 t + (row >> 4), column row & 15
+            const f32x4 v = *reinterpret_cast<const f32x4*>(scr + row * 32 + 4 * tc);
+            const int y = y0 + 4 * wm + 2 * t + (row >> 4), x = x0 + (row & 15);
+            if (y < p.H && x < p.W && nb * 64 + wn * 32 + 4 * tc < p.Cout)
+                *reinterpret_cast<f32x4*>(out_t + ((size_t)y * p.W + x) * p.out_stride + 4 * tc) = v;
+        }
+    }
+}
+
+int launch_conv3x3_dil2(const ConvParams& pin, hipStream_t stream) {
+    ConvParams p = pin;
+    GTSFM_CHECK_ARG(p.Cin % 64 == 0 && p.Cin >= 64, "conv3x3_dil2: Cin must be a multiple of 64 (got %d)", p.Cin);
+    GTSFM_CHECK_ARG(p.in_stride % 4 == 0 && p.in_coff % 4 == 0, "conv3x3_dil2: input stride/offset must be 16-byte aligned");
+    GTSFM_CHECK_ARG(((p.Cout | p.out_stride | p.out_coff) & 3) == 0, "conv3x3_dil2: output channels/stride/offset must be multiples of 4");
+    GTSFM_CHECK_ARG(!p.pool && !p.img, "conv3x3_dil2: no fused pool or first layer");
+    p.tiles_x = ceil_div(p.W, CV_TW);
+    p.tiles_y = ceil_div(p.H, CV_TH);
+    dim3 grid(p.B * p.tiles_x * p.tiles_y, ceil_div(p.Cout, 64));
+    const size_t lds_bytes = (size_t)CD_HALO_FLOATS * sizeof(float);
+    // more than 64 KiB of dynamic LDS has to be allowed, once per device (bit d of `allowed`: done on device d; a process may hold engines on several)
+    static std::atomic<unsigned long long> allowed{0};
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) dev = 64;
+    if (dev < 0 || dev >= 64 || !((allowed.load(std::memory_order_relaxed) >> dev) & 1ull)) {
+        const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(conv3x3_dil2_mfma_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
+        if (attr != hipSuccess) {
+            (void)hipGetLastError();
+            gtsfm_set_error("conv3x3_dil2: cannot allow %zu bytes of dynamic LDS: %s", lds_bytes, hipGetErrorString(attr));
+            return GTSFM_ERR_HIP;
+        }
+        if (dev >= 0 && dev < 64) allowed.fetch_or(1ull << dev, std::memory_order_relaxed);
+    }
+    hipLaunchKernelGGL(conv3x3_dil2_mfma_kernel, grid, dim3(256), lds_bytes, stream, p);
+    GTSFM_CHECK_LAUNCH("conv3x3_dil2_mfma_kernel");
     return GTSFM_OK;
 }
 

@@ -1,0 +1,1 @@
+from gtsfm_amd.frontend.detector_descriptor.d2net import D2NetDetDesc  # noqa: F401

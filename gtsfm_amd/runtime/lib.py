@@ -203,6 +203,29 @@ SIGNATURES = {
         [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t,
          C.c_void_p],
     ),
+    "gtsfm_conv3x3_dil2_f32": (
+        C.c_int,
+        [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+         C.c_void_p],
+    ),
+    "gtsfm_d2net_packed_weight_floats": (C.c_size_t, []),
+    "gtsfm_d2net_pack_weights": (C.c_int, [C.POINTER(C.c_void_p), C.c_void_p]),
+    "gtsfm_d2net_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    "gtsfm_d2net_forward": (
+        C.c_int,
+        [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+         C.c_size_t, C.c_void_p],
+    ),
+    "gtsfm_d2net_stage": (
+        C.c_int,
+        [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p],
+    ),
+    "gtsfm_d2net_detect_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int]),
+    "gtsfm_d2net_detect": (
+        C.c_int,
+        [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
+         C.c_void_p],
+    ),
 }
 
 

@@ -498,6 +498,68 @@ int gtsfm_megaloc_forward(const float* packed_weights_dev, int depth, int feat_d
 int gtsfm_megaloc_stage(const float* packed_weights_dev, int depth, int feat_dim, const float* pos_dev, const void* image_dev, int layout, int batch, int height,
                         int width, int stage, float* out_dev, void* workspace_dev, size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * D2-Net detector-descriptor, single scale
+ *   DM = thirdparty/d2net/lib/model_test.py, DP = thirdparty/d2net/lib/pyramid.py, DU = thirdparty/d2net/lib/utils.py,
+ *   DG = gtsfm/frontend/detector_descriptor/d2net.py
+ * The dense map of a height x width image is [(height / 2) / 2 - 1][(width / 2) / 2 - 1][512] (floor at both max-pools, then the
+ * stride-1 average pool). A candidate record is six 32-bit words: int32 channel, i, j; float step_i, step_j, score.
+ * ---------------------------------------------------------------------------------------------------------- */
+
+/* gtsfm_conv3x3_f32 with dilation 2 and zero pad 2 (DM:34-38): out = relu?(conv(in) + bias), same NHWC layouts and the same packed
+ * weights (gtsfm_pack_conv3x3; the packing does not depend on the dilation); no pool; cout, out_stride and out_coff multiples of 4; bias_dev holds ceil(cout / 64) * 64 floats (padded, as for gtsfm_conv3x3_f32).
+ * Every 64-channel chunk of the input is summed on its own and the chunk sums are added in order, starting from the bias. */
+int gtsfm_conv3x3_dil2_f32(const float* in_dev, int in_stride, int in_coff, float* out_dev, int out_stride, int out_coff, const float* packed_w_dev,
+                           const float* bias_dev, int batch, int h, int w, int cin, int cout, int relu, void* stream);
+
+/* Packed D2-Net weights (floats) and the packer. tensors_host, torch layouts, 21 tensors in this order: the ten convolutions
+ * conv1_1 .. conv3_3, conv4_1 .. conv4_3 (DM:17-38) as (weight [out][in][3][3], bias [out]) pairs, then the uint8 normalisation
+ * table [3][256] float32: entry [c][v] = float32(((float32(v) / 255) - mean[c]) / std[c]) evaluated as DU:23-38 does (the division
+ * by 255 in float32, the rest in float64).                                                                   replaces DM:16-40 */
+size_t gtsfm_d2net_packed_weight_floats(void);
+int gtsfm_d2net_pack_weights(const float* const* tensors_host, float* packed_host);
+
+/* Bytes of device workspace a forward / stage call needs (0 for a shape the calls refuse, with the reason in gtsfm_last_error: batch >= 1,
+ * height, width >= 8, cand_capacity >= 1, batch * cand_capacity <= 2^28, batch * ceil(height / 8) * ceil(width / 16) < 2^31). cand_capacity: the number of candidate records per image the call can hold. */
+size_t gtsfm_d2net_workspace_bytes(int batch, int height, int width, int cand_capacity);
+
+/* D2Net.dense_feature_extraction + process_multiscale(scales = [1]) + the top-k of DG:84-87 for a batch of equally-sized images,
+ * exact fp32.                                                                 replaces DM:47-58,110-200, DP:48-128, DU:89-177, DG:84-95
+ * layout 0: image_dev [batch][3][height][width] float32, already normalised (DU:35-38).
+ * layout 1: image_dev [batch][height][width][3] uint8, normalised through the packed table: equals the reference's input bit for bit.
+ * layout 2: image_dev [batch][height][width] uint8, a gray image: the same value in the three channels (DG:113-116).
+ * A detection is a (pixel, channel) whose value equals the pixel's channel maximum and the 3 x 3 maximum of its channel (-inf
+ * outside the map), with det > 0 and tr * tr / det <= 7.2f of the Hessian (zeros outside the map), whose Newton step -H^-1 g is
+ * below 0.5 in both components and whose four bilinear corners lie inside the map. Arithmetic, in this order:
+ *   dii = (up - 2 x) + down, djj = (left - 2 x) + right, dij = 0.25 (((x[-1,-1] - x[-1,+1]) - x[+1,-1]) + x[+1,+1]),
+ *   det = dii djj - dij dij, di = 0.5 down - 0.5 up, dj = 0.5 right - 0.5 left,
+ *   step_i = -((djj / det) di + (-dij / det) dj), step_j = -((-dij / det) di + (dii / det) dj).
+ * The candidates are sorted by score descending, EQUAL SCORES BY (channel, i, j) ASCENDING (np.argsort in DG:84 is not stable and
+ * makes no promise); the first min(count, max_keypoints) are kept.
+ * counts_dev [batch] int32: the number of candidates FOUND per image. When one exceeds cand_capacity that image's outputs are
+ *   incomplete and the call has to be repeated with at least that capacity; nothing is truncated silently. The number of
+ *   keypoints of an image is min(counts_dev[b], max_keypoints).
+ * keypoints_dev [batch][max_keypoints][2] (x, y) = ((p * 2 + 0.5) * 2 + 0.5 of (j, i) + step), scores_dev [batch][max_keypoints],
+ * desc_dev [batch][max_keypoints][512] unit rows (bilinear interpolation DU:149-164 left to right, x / max(||x||, 1e-12)).
+ * Per image, the result does not depend on the batch. */
+int gtsfm_d2net_forward(const float* packed_weights_dev, const void* image_dev, int layout, int batch, int height, int width, int max_keypoints,
+                        int cand_capacity, int32_t* counts_dev, float* keypoints_dev, float* scores_dev, float* desc_dev, void* workspace_dev,
+                        size_t workspace_bytes, void* stream);
+
+/* The stages of gtsfm_d2net_forward (same kernels), for stage-wise tests. stage 0: relu(conv1_1(normalised image)),
+ * [batch][height][width][64] NHWC; 1: relu(conv3_3), [batch][height / 4][width / 4][256]; 2: the dense map, [batch][H2][W2][512];
+ * 3: the sorted candidate list, out_dev [batch][cand_capacity] records of which the first min(counts_dev[b], cand_capacity) are
+ * written, and counts_dev [batch] (used by stage 3 only). */
+int gtsfm_d2net_stage(const float* packed_weights_dev, const void* image_dev, int layout, int batch, int height, int width, int stage, int cand_capacity,
+                      void* out_dev, int32_t* counts_dev, void* workspace_dev, size_t workspace_bytes, void* stream);
+
+/* The detection head alone on a caller's dense map map_dev [batch][map_height][map_width][512]: counts_dev as above,
+ * candidates_dev (optional) [batch][cand_capacity] sorted records, and for max_keypoints > 0 the three keypoint outputs. */
+size_t gtsfm_d2net_detect_workspace_bytes(int batch, int cand_capacity);
+int gtsfm_d2net_detect(const float* map_dev, int batch, int map_height, int map_width, int max_keypoints, int cand_capacity, int32_t* counts_dev,
+                       void* candidates_dev, float* keypoints_dev, float* scores_dev, float* desc_dev, void* workspace_dev, size_t workspace_bytes,
+                       void* stream);
+
 #ifdef __cplusplus
 }
 #endif
