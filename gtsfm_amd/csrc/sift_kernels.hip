@@ -1,0 +1,789 @@
+// SIFT detector-descriptor with OpenCV's SIFT_create() defaults (nOctaveLayers 3, contrastThreshold 0.04, edgeThreshold 10, sigma 1.6,
+// float32 pyramid, first octave -1): the device side of gtsfm_amd.frontend.detector_descriptor.SIFTDetectorDescriptor.
+// See include/gtsfm_amd.h; tests/sift_reference.py restates every stage in numpy in the same operation order.
+//
+// One image at a time on the caller's stream (a batch is a loop, so a batch equals its images one at a time by construction):
+//   1. sift_upsample_kernel : gray uint8 -> float32, 2 x bilinear with half-pixel centres (weights 0.25 / 0.75: exact in float32).
+//   2. sift_blur_row/col    : separable Gaussian, BORDER_REFLECT_101 with repeated reflection, taps built on the host in float64. The
+//                             sum runs from the centre outwards: acc = k0 c; acc = acc + k_j (left_j + right_j), j = 1 .. r.
+//   3. sift_decimate_kernel : the next octave's base = every second pixel of Gaussian image 3.
+//   4. sift_dog_kernel      : D[i] = G[i + 1] - G[i].
+//   5. sift_extrema_kernel  : one thread per interior pixel of DoG layers 1 .. 3; candidates (octave, layer, row, column) go to a list
+//                             through an integer counter, in any order.
+//   6. sift_refine_kernel   : one thread per candidate: up to five Newton steps (3 x 3 elimination with partial pivoting), contrast and
+//                             edge tests. Candidates that converge to the same (octave, layer, row, column) are identical records; a bit
+//                             per position (atomicOr) keeps exactly one.
+//   7. sift_orient_kernel   : one wave per keypoint: the 36-bin histogram is owner-computes (lane b adds the samples of bin b in window
+//                             order), smoothing, peaks. The mask test (runByPixelsMask) sits here. One record per peak, any order.
+//   8. sift_rank_kernel     : records sorted by (response descending; octave, layer, row, column, angle ascending): keys are unique, so
+//                             every record counts the records before it and is written to its rank. Deterministic.
+//   9. sift_describe_kernel : one wave per kept keypoint: the 6 x 6 x 10 histogram lives in LDS, lane s owns spatial cell s and adds the
+//                             samples that touch it in window order; fold, clip at 0.2, x 512, round to nearest even, saturate.
+// No floating-point atomics anywhere. exp, exp2, sin and cos are explicit float32 polynomials (the restatement uses the same ones), sqrt
+// and division are correctly rounded, and -ffp-contract=off keeps a * b + c two roundings: the device equals the restatement bit for bit.
+
+#include <float.h>
+#include <math.h>
+
+#include "../../include/gtsfm_amd.h"
+#include "common.h"
+
+#define SIFT_MAX_OCTAVES 16
+#define SIFT_MAX_RADIUS 15  // of a blur; the largest the pyramid needs is 13
+#define SIFT_BORDER 5
+#define SIFT_LAYERS 3
+#define SIFT_MAX_EDGE 32767  // the doubled image has to fit a launch grid's y extent
+
+namespace {
+
+struct SiftOct {
+    int H, W, diag, pad;     // diag = (int)sqrt(W^2 + H^2), the cap of a descriptor's radius
+    long long g, d, claim;   // float offsets of the octave's 6 Gaussian and 5 DoG images; bit offset of its 3 x H x W claim bits
+};
+struct SiftGeom {
+    int n, H2, W2, pad;
+    long long floats, claim_words;  // the whole pyramid; the claim bitmap in 32-bit words
+    SiftOct o[SIFT_MAX_OCTAVES];
+};
+struct SiftTaps {
+    int r;
+    float k[SIFT_MAX_RADIUS + 1];  // k[0] the centre tap, k[j] the tap at distance j
+};
+struct SiftKp {  // a refined keypoint, octave coordinates
+    int32_t o, l, r, c;
+    float x, y, scl, resp;  // x = c + X0, y = r + X1, scl = 1.6 * 2^((l + X2) / 3)
+};
+struct SiftOri {  // an oriented keypoint
+    int32_t o, l, r, c;
+    float x, y, scl, resp, angle, pad;
+};
+static_assert(sizeof(SiftKp) == 32 && sizeof(SiftOri) == 40, "records are 8 and 10 32-bit words");
+
+int sift_round_half_even(double v) { return (int)nearbyint(v); }
+
+// Octave sizes and offsets. nOctaves = round(log2(min(H2, W2))) - 2 on the doubled size.
+SiftGeom sift_geometry(int H, int W) {
+    SiftGeom g = {};
+    g.H2 = 2 * H, g.W2 = 2 * W;
+    int n = sift_round_half_even(log2((double)(g.H2 < g.W2 ? g.H2 : g.W2))) - 2;
+    if (n < 0) n = 0;
+    if (n > SIFT_MAX_OCTAVES) n = SIFT_MAX_OCTAVES;
+    g.n = n;
+    long long off = 0, bits = 0;
+    int h = g.H2, w = g.W2;
+    for (int o = 0; o < n; ++o) {
+        if (h < 1 || w < 1) {
+            g.n = o;
+            break;
+        }
+        g.o[o].H = h, g.o[o].W = w;
+        g.o[o].diag = (int)sqrt((double)w * w + (double)h * h);
+        g.o[o].g = off, off += 6LL * h * w;
+        g.o[o].claim = bits, bits += 3LL * h * w;
+        h /= 2, w /= 2;
+    }
+    for (int o = 0; o < g.n; ++o) g.o[o].d = off, off += 5LL * g.o[o].H * g.o[o].W;
+    g.floats = off;
+    g.claim_words = (bits + 31) / 32;
+    return g;
+}
+
+// Taps exp(-x^2 / 2 sigma^2) / sum in float64 (the sum taken left to right), rounded to float32; round(8 sigma + 1) | 1 of them.
+SiftTaps sift_taps(double sigma) {
+    SiftTaps t = {};
+    const int n = sift_round_half_even(8.0 * sigma + 1.0) | 1;
+    t.r = n / 2;
+    if (t.r > SIFT_MAX_RADIUS) t.r = SIFT_MAX_RADIUS;  // never for sigma 1.6 and three layers
+    double w[2 * SIFT_MAX_RADIUS + 1], sum = 0.0;
+    for (int i = 0; i < 2 * t.r + 1; ++i) {
+        const double x = (double)(i - t.r);
+        w[i] = exp(-(x * x) / (2.0 * sigma * sigma));
+        sum += w[i];
+    }
+    for (int j = 0; j <= t.r; ++j) t.k[j] = (float)(w[t.r + j] / sum);
+    return t;
+}
+
+double sift_layer_sigma(int i) {  // i = 0: the base blur of the doubled image; i = 1 .. 5: the increment from image i - 1 to image i
+    if (i == 0) {
+        const double d = 1.6 * 1.6 - 1.0 * 1.0;
+        return sqrt(d > 0.01 ? d : 0.01);
+    }
+    const double k = pow(2.0, 1.0 / 3.0);
+    const double prev = pow(k, (double)(i - 1)) * 1.6, total = prev * k;
+    return sqrt(total * total - prev * prev);
+}
+
+// Workspace (bytes, 256-aligned pieces): pyramid | two full-size temporaries | claim bits | candidates | keypoints | oriented | sorted | counts.
+struct SiftWs {
+    size_t pyr, tmpA, tmpB, claim, cand, kps, ori, sorted, counts, total;
+};
+
+SiftWs sift_ws(const SiftGeom& g, int cand_cap, int kp_cap) {
+    SiftWs s;
+    size_t o = 0;
+    const size_t full = align_up((size_t)g.H2 * g.W2 * 4, 256);
+    s.pyr = o, o += align_up((size_t)g.floats * 4 + 4, 256);
+    s.tmpA = o, o += full;
+    s.tmpB = o, o += full;
+    s.claim = o, o += align_up((size_t)g.claim_words * 4 + 4, 256);
+    s.cand = o, o += align_up((size_t)cand_cap * 16, 256);
+    s.kps = o, o += align_up((size_t)kp_cap * sizeof(SiftKp), 256);
+    s.ori = o, o += align_up((size_t)kp_cap * sizeof(SiftOri), 256);
+    s.sorted = o, o += align_up((size_t)kp_cap * sizeof(SiftOri), 256);
+    s.counts = o, o += 256;
+    s.total = o;
+    return s;
+}
+
+// ------------------------------------------------------------------------------------------------------------------------------
+// explicit float32 mathematics, restated one to one in tests/sift_reference.py
+// ------------------------------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ float sift_exp2(float t) {
+    const float n = rintf(t);
+    const float g = (t - n) * 0.6931471805599453f;
+    float p = (float)(1.0 / 5040.0);
+    p = p * g + (float)(1.0 / 720.0);
+    p = p * g + (float)(1.0 / 120.0);
+    p = p * g + (float)(1.0 / 24.0);
+    p = p * g + (float)(1.0 / 6.0);
+    p = p * g + 0.5f;
+    p = p * g + 1.0f;
+    p = p * g + 1.0f;
+    return ldexpf(p, (int)n);
+}
+__device__ __forceinline__ float sift_exp(float x) { return sift_exp2(x * 1.4426950408889634f); }
+
+// OpenCV's fastAtan2 polynomial, degrees in [0, 360).
+__device__ __forceinline__ float sift_atan2_deg(float y, float x) {
+    const float scale = (float)(180.0 / 3.14159265358979323846);
+    const float p1 = 0.9997878412794807f * scale, p3 = -0.3258083974640975f * scale, p5 = 0.1555786518463281f * scale, p7 = -0.04432655554792128f * scale;
+    const float ax = fabsf(x), ay = fabsf(y);
+    const float mn = fminf(ax, ay), mx = fmaxf(ax, ay);
+    const float a = mn / (mx + 2.220446049250313e-16f);
+    const float a2 = a * a;
+    float p = (((p7 * a2 + p5) * a2 + p3) * a2 + p1) * a;
+    if (ay > ax) p = 90.0f - p;
+    if (x < 0.0f) p = 180.0f - p;
+    if (y < 0.0f) p = 360.0f - p;
+    return p;
+}
+
+// cos and sin of an angle in degrees: quadrant reduction, then Taylor polynomials on [-45, 45] degrees.
+__device__ __forceinline__ void sift_sincos_deg(float a, float* cs, float* sn) {
+    const float q = rintf(a / 90.0f);
+    const float t = (a - 90.0f * q) * (float)(3.14159265358979323846 / 180.0);
+    const float t2 = t * t;
+    float s = (float)(1.0 / 362880.0);
+    s = s * t2 + (float)(-1.0 / 5040.0);
+    s = s * t2 + (float)(1.0 / 120.0);
+    s = s * t2 + (float)(-1.0 / 6.0);
+    s = s * t2 * t + t;
+    float c = (float)(-1.0 / 3628800.0);
+    c = c * t2 + (float)(1.0 / 40320.0);
+    c = c * t2 + (float)(-1.0 / 720.0);
+    c = c * t2 + (float)(1.0 / 24.0);
+    c = c * t2 + -0.5f;
+    c = c * t2 + 1.0f;
+    const int qi = ((int)q) & 3;
+    *cs = qi == 0 ? c : qi == 1 ? -s : qi == 2 ? -c : s;
+    *sn = qi == 0 ? s : qi == 1 ? c : qi == 2 ? -s : -c;
+}
+
+__device__ __forceinline__ int sift_reflect101(int p, int n) {
+    if (n == 1) return 0;
+    while ((unsigned)p >= (unsigned)n) p = p < 0 ? -p : 2 * n - 2 - p;
+    return p;
+}
+
+// ------------------------------------------------------------------------------------------------------------------------------
+// pyramid
+// ------------------------------------------------------------------------------------------------------------------------------
+// grid (ceil(2W / 256), 2H). Source coordinate (d + 0.5) / 2 - 0.5: even d = 2k takes 0.25 I[k - 1] + 0.75 I[k], odd d = 2k + 1 takes
+// 0.75 I[k] + 0.25 I[k + 1], edges clamped. Every intermediate is a multiple of 1/16 below 256: exact.
+__global__ __launch_bounds__(256) void sift_upsample_kernel(const uint8_t* __restrict__ gray, int H, int W, float* __restrict__ out) {
+    const int x = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y;
+    if (x >= 2 * W) return;
+    const int kx = x >> 1, ky = y >> 1;
+    const int x0 = (x & 1) ? kx : max(kx - 1, 0), x1 = (x & 1) ? min(kx + 1, W - 1) : kx;
+    const int y0 = (y & 1) ? ky : max(ky - 1, 0), y1 = (y & 1) ? min(ky + 1, H - 1) : ky;
+    const float wx0 = (x & 1) ? 0.75f : 0.25f, wx1 = 1.0f - wx0, wy0 = (y & 1) ? 0.75f : 0.25f, wy1 = 1.0f - wy0;
+    const float top = wx0 * (float)gray[(size_t)y0 * W + x0] + wx1 * (float)gray[(size_t)y0 * W + x1];
+    const float bot = wx0 * (float)gray[(size_t)y1 * W + x0] + wx1 * (float)gray[(size_t)y1 * W + x1];
+    out[(size_t)y * (2 * W) + x] = wy0 * top + wy1 * bot;
+}
+
+// grid (ceil(W / 256), H)
+__global__ __launch_bounds__(256) void sift_blur_row_kernel(const float* __restrict__ in, float* __restrict__ out, int H, int W, SiftTaps taps) {
+    __shared__ float k[SIFT_MAX_RADIUS + 1];
+    if (threadIdx.x <= SIFT_MAX_RADIUS) k[threadIdx.x] = taps.k[threadIdx.x];
+    __syncthreads();
+    const int x = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y;
+    if (x >= W) return;
+    const float* row = in + (size_t)y * W;
+    float acc = k[0] * row[x];
+    for (int j = 1; j <= taps.r; ++j) {
+        const float a = row[sift_reflect101(x - j, W)], b = row[sift_reflect101(x + j, W)];
+        acc = acc + k[j] * (a + b);
+    }
+    out[(size_t)y * W + x] = acc;
+}
+
+__global__ __launch_bounds__(256) void sift_blur_col_kernel(const float* __restrict__ in, float* __restrict__ out, int H, int W, SiftTaps taps) {
+    __shared__ float k[SIFT_MAX_RADIUS + 1];
+    if (threadIdx.x <= SIFT_MAX_RADIUS) k[threadIdx.x] = taps.k[threadIdx.x];
+    __syncthreads();
+    const int x = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y;
+    if (x >= W) return;
+    float acc = k[0] * in[(size_t)y * W + x];
+    for (int j = 1; j <= taps.r; ++j) {
+        const float a = in[(size_t)sift_reflect101(y - j, H) * W + x], b = in[(size_t)sift_reflect101(y + j, H) * W + x];
+        acc = acc + k[j] * (a + b);
+    }
+    out[(size_t)y * W + x] = acc;
+}
+
+// out [h][w] = in [2y][2x]; in is H x W with h = H / 2, w = W / 2. grid (ceil(w / 256), h)
+__global__ __launch_bounds__(256) void sift_decimate_kernel(const float* __restrict__ in, int W, float* __restrict__ out, int w) {
+    const int x = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y;
+    if (x >= w) return;
+    out[(size_t)y * w + x] = in[(size_t)(2 * y) * W + 2 * x];
+}
+
+// d [5][H][W] = g [1 .. 5] - g [0 .. 4]
+__global__ __launch_bounds__(256) void sift_dog_kernel(const float* __restrict__ g, float* __restrict__ d, size_t plane, size_t total) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= total) return;
+    d[i] = g[i + plane] - g[i];
+}
+
+// ------------------------------------------------------------------------------------------------------------------------------
+// detection
+// ------------------------------------------------------------------------------------------------------------------------------
+// grid (ceil((W - 10) / 256), H - 10, 3): DoG layer 1 + z, row 5 + y. counts[0] counts every candidate, written or not.
+__global__ __launch_bounds__(256) void sift_extrema_kernel(const float* __restrict__ dog, int H, int W, int o, int cap, int* __restrict__ counts,
+                                                         int4* __restrict__ cand) {
+    const int c = SIFT_BORDER + blockIdx.x * 256 + threadIdx.x, r = SIFT_BORDER + blockIdx.y, l = 1 + blockIdx.z;
+    if (c >= W - SIFT_BORDER) return;
+    const size_t plane = (size_t)H * W;
+    const float* p = dog + (size_t)l * plane + (size_t)r * W + c;
+    const float v = *p;
+    if (!(fabsf(v) > 1.0f)) return;  // floor(0.5 * 0.04 / 3 * 255) = 1
+    bool is_max = v > 0.0f, is_min = v < 0.0f;
+    for (int dl = -1; dl <= 1; ++dl)
+        for (int dr = -1; dr <= 1; ++dr)
+            for (int dc = -1; dc <= 1; ++dc) {
+                const float nb = p[(long long)dl * (long long)plane + (long long)dr * W + dc];
+                is_max = is_max && v >= nb;
+                is_min = is_min && v <= nb;
+            }
+    if (!(is_max || is_min)) return;
+    const int idx = atomicAdd(counts, 1);
+    if (idx < cap) cand[idx] = make_int4(o, l, r, c);
+}
+
+// X = A^-1 b by elimination with partial pivoting, in this order (a singular system gives X = 0).
+__device__ __forceinline__ void sift_solve3(float A[3][3], float b[3]) {
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        int k = i;
+#pragma unroll
+        for (int j = i + 1; j < 3; ++j)
+            if (fabsf(A[j][i]) > fabsf(A[k][i])) k = j;
+        if (fabsf(A[k][i]) < FLT_EPSILON * 10.0f) {
+            b[0] = b[1] = b[2] = 0.0f;
+            return;
+        }
+#pragma unroll
+        for (int j = i + 1; j < 3; ++j)
+            if (k == j) {
+#pragma unroll
+                for (int q = 0; q < 3; ++q) {
+                    const float t = A[i][q];
+                    A[i][q] = A[j][q], A[j][q] = t;
+                }
+                const float t = b[i];
+                b[i] = b[j], b[j] = t;
+            }
+        const float d = -1.0f / A[i][i];
+#pragma unroll
+        for (int j = i + 1; j < 3; ++j) {
+            const float alpha = A[j][i] * d;
+#pragma unroll
+            for (int q = i + 1; q < 3; ++q) A[j][q] = A[j][q] + alpha * A[i][q];
+            b[j] = b[j] + alpha * b[i];
+        }
+    }
+#pragma unroll
+    for (int i = 2; i >= 0; --i) {
+        float s = b[i];
+#pragma unroll
+        for (int q = i + 1; q < 3; ++q) s = s - A[i][q] * b[q];
+        b[i] = s / A[i][i];
+    }
+}
+
+// One thread per candidate. counts[1] counts every keypoint, written or not.
+__global__ __launch_bounds__(256) void sift_refine_kernel(const float* __restrict__ pyr, SiftGeom geom, const int4* __restrict__ cand, int cand_cap, int kp_cap,
+                                                        int* __restrict__ counts, unsigned* __restrict__ claim, SiftKp* __restrict__ kps) {
+    __shared__ SiftOct oct[SIFT_MAX_OCTAVES];
+    if (threadIdx.x < SIFT_MAX_OCTAVES) oct[threadIdx.x] = geom.o[threadIdx.x];
+    __syncthreads();
+    const int n = min(counts[0], cand_cap);
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const int4 cd = cand[i];
+    const int o = cd.x;
+    int l = cd.y, r = cd.z, c = cd.w;
+    const int H = oct[o].H, W = oct[o].W;
+    const size_t plane = (size_t)H * W;
+    const float* dog = pyr + oct[o].d;
+    const float img_scale = 1.0f / 255.0f, deriv_scale = img_scale * 0.5f, second_scale = img_scale, cross_scale = img_scale * 0.25f;
+    const float limit = (float)(2147483647 / 3);
+    float xc = 0.f, xr = 0.f, xi = 0.f, dx = 0.f, dy = 0.f, ds = 0.f, dxx = 0.f, dyy = 0.f, dxy = 0.f, v = 0.f;
+    bool converged = false;
+    for (int it = 0; it < 5; ++it) {
+        const float* img = dog + (size_t)l * plane + (size_t)r * W + c;
+        const float* prv = img - plane;
+        const float* nxt = img + plane;
+        v = img[0];
+        dx = (img[1] - img[-1]) * deriv_scale;
+        dy = (img[W] - img[-W]) * deriv_scale;
+        ds = (nxt[0] - prv[0]) * deriv_scale;
+        const float v2 = v * 2.0f;
+        dxx = (img[1] + img[-1] - v2) * second_scale;
+        dyy = (img[W] + img[-W] - v2) * second_scale;
+        const float dss = (nxt[0] + prv[0] - v2) * second_scale;
+        dxy = (img[W + 1] - img[W - 1] - img[-W + 1] + img[-W - 1]) * cross_scale;
+        const float dxs = (nxt[1] - nxt[-1] - prv[1] + prv[-1]) * cross_scale;
+        const float dys = (nxt[W] - nxt[-W] - prv[W] + prv[-W]) * cross_scale;
+        float A[3][3] = {{dxx, dxy, dxs}, {dxy, dyy, dys}, {dxs, dys, dss}};
+        float b[3] = {dx, dy, ds};
+        sift_solve3(A, b);
+        xc = -b[0], xr = -b[1], xi = -b[2];
+        if (fabsf(xi) < 0.5f && fabsf(xr) < 0.5f && fabsf(xc) < 0.5f) {
+            converged = true;
+            break;
+        }
+        if (!(fabsf(xi) <= limit && fabsf(xr) <= limit && fabsf(xc) <= limit)) return;
+        c += (int)rintf(xc), r += (int)rintf(xr), l += (int)rintf(xi);
+        if (l < 1 || l > SIFT_LAYERS || c < SIFT_BORDER || c >= W - SIFT_BORDER || r < SIFT_BORDER || r >= H - SIFT_BORDER) return;
+    }
+    if (!converged) return;
+    const float t = (dx * xc + dy * xr) + ds * xi;
+    const float contr = v * img_scale + t * 0.5f;
+    if ((double)(fabsf(contr) * 3.0f) < 0.04) return;
+    const float tr = dxx + dyy, det = dxx * dyy - dxy * dxy;
+    if (det <= 0.0f || (double)(tr * tr) * 10.0 >= 121.0 * (double)det) return;
+    const long long bit = oct[o].claim + ((long long)(l - 1) * H + r) * W + c;
+    const unsigned m = 1u << (unsigned)(bit & 31);
+    if (atomicOr(claim + (bit >> 5), m) & m) return;  // another candidate arrived here first with the same record
+    const int idx = atomicAdd(counts + 1, 1);
+    if (idx >= kp_cap) return;
+    SiftKp kp;
+    kp.o = o, kp.l = l, kp.r = r, kp.c = c;
+    kp.x = (float)c + xc, kp.y = (float)r + xr;
+    kp.scl = 1.6f * sift_exp2(((float)l + xi) / 3.0f);
+    kp.resp = fabsf(contr);
+    kps[idx] = kp;
+}
+
+// One wave per keypoint (64 threads). counts[2] counts every oriented keypoint, written or not. mask: [H0][W0] uint8 or null.
+__global__ __launch_bounds__(64) void sift_orient_kernel(const float* __restrict__ pyr, SiftGeom geom, const SiftKp* __restrict__ kps, int kp_cap,
+                                                       const uint8_t* __restrict__ mask, int H0, int W0, int* __restrict__ counts,
+                                                       SiftOri* __restrict__ out) {
+    __shared__ int s_bin[64];
+    __shared__ float s_val[64];
+    __shared__ float raw[36], sm[36];
+    const int n = min(counts[1], kp_cap);
+    const int k = blockIdx.x, lane = threadIdx.x;
+    if (k >= n) return;
+    const SiftKp kp = kps[k];
+    if (mask) {  // on the final coordinates: (x, y) * 2^o * 0.5
+        const int mx = min(max((int)rintf(ldexpf(kp.x, kp.o - 1)), 0), W0 - 1), my = min(max((int)rintf(ldexpf(kp.y, kp.o - 1)), 0), H0 - 1);
+        if (mask[(size_t)my * W0 + mx] == 0) return;
+    }
+    const SiftOct oc = geom.o[kp.o];
+    const int H = oc.H, W = oc.W;
+    const float* img = pyr + oc.g + (size_t)kp.l * H * W;
+    const int radius = (int)rintf(4.5f * kp.scl);
+    const float sigma = 1.5f * kp.scl;
+    const float expf_scale = -1.0f / (2.0f * sigma * sigma);
+    const int side = 2 * radius + 1, total = side * side;
+    float h = 0.0f;
+    for (int base = 0; base < total; base += 64) {
+        const int idx = base + lane;
+        int bin = -1;
+        float val = 0.0f;
+        if (idx < total) {
+            const int i = idx / side - radius, j = idx % side - radius;
+            const int y = kp.r + i, x = kp.c + j;
+            if (y > 0 && y < H - 1 && x > 0 && x < W - 1) {
+                const float* p = img + (size_t)y * W + x;
+                const float dx = p[1] - p[-1], dy = p[-W] - p[W];
+                const float w = sift_exp((float)(i * i + j * j) * expf_scale);
+                const float ang = sift_atan2_deg(dy, dx);
+                const float mag = sqrtf(dx * dx + dy * dy);
+                bin = (int)rintf((36.0f / 360.0f) * ang);
+                if (bin >= 36) bin -= 36;
+                if (bin < 0) bin += 36;
+                val = w * mag;
+            }
+        }
+        __syncthreads();
+        s_bin[lane] = bin, s_val[lane] = val;
+        __syncthreads();
+        const int m = min(64, total - base);
+        for (int s = 0; s < m; ++s)
+            if (s_bin[s] == lane) h = h + s_val[s];
+    }
+    if (lane < 36) raw[lane] = h;
+    __syncthreads();
+    float hs = 0.0f;
+    if (lane < 36) {
+        const float m2 = raw[(lane + 34) % 36], m1 = raw[(lane + 35) % 36], p1 = raw[(lane + 1) % 36], p2 = raw[(lane + 2) % 36];
+        hs = (m2 + p2) * (1.0f / 16.0f) + (m1 + p1) * (4.0f / 16.0f) + raw[lane] * (6.0f / 16.0f);
+        sm[lane] = hs;
+    }
+    __syncthreads();
+    const float omax = wave_max(lane < 36 ? hs : -FLT_MAX);
+    const float thr = omax * 0.8f;
+    bool peak = false;
+    float angle = 0.0f;
+    if (lane < 36) {
+        const float hl = sm[(lane + 35) % 36], hr = sm[(lane + 1) % 36];
+        if (hs > hl && hs > hr && hs >= thr) {
+            peak = true;
+            float bin = (float)lane + 0.5f * (hl - hr) / (hl - 2.0f * hs + hr);
+            bin = bin < 0.0f ? 36.0f + bin : bin >= 36.0f ? bin - 36.0f : bin;
+            angle = 360.0f - (360.0f / 36.0f) * bin;
+            if (fabsf(angle - 360.0f) < FLT_EPSILON) angle = 0.0f;
+        }
+    }
+    const unsigned long long peaks = __ballot(peak);
+    if (peaks == 0) return;
+    int start = 0;
+    if (lane == 0) start = atomicAdd(counts + 2, __popcll(peaks));
+    start = __shfl(start, 0, 64);
+    if (peak) {
+        const int slot = start + __popcll(peaks & ((1ull << lane) - 1ull));
+        if (slot < kp_cap) {
+            SiftOri r;
+            r.o = kp.o, r.l = kp.l, r.r = kp.r, r.c = kp.c;
+            r.x = kp.x, r.y = kp.y, r.scl = kp.scl, r.resp = kp.resp, r.angle = angle, r.pad = 0.0f;
+            out[slot] = r;
+        }
+    }
+}
+
+// (response descending; octave, layer, row, column, angle ascending) as two 64-bit keys; responses and angles are >= 0, so their bits order them.
+__device__ __forceinline__ void sift_keys(const SiftOri& r, unsigned long long* a, unsigned long long* b) {
+    *a = ((unsigned long long)(0xFFFFFFFFu - __float_as_uint(r.resp)) << 32) | (unsigned)(r.o * 4 + r.l);
+    *b = ((unsigned long long)(unsigned)r.r << 48) | ((unsigned long long)(unsigned)r.c << 32) | __float_as_uint(r.angle);
+}
+
+// sorted[rank] = ori[t], rank = the number of records before t. grid ceil(cap / 256).
+__global__ __launch_bounds__(256) void sift_rank_kernel(const SiftOri* __restrict__ ori, const int* __restrict__ counts, int cap, SiftOri* __restrict__ sorted) {
+    __shared__ unsigned long long sa[256], sb[256];
+    const int n = min(counts[2], cap);
+    if ((int)(blockIdx.x * 256) >= n) return;  // the whole workgroup
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    SiftOri mine = {};
+    unsigned long long ma = 0, mb = 0;
+    if (t < n) {
+        mine = ori[t];
+        sift_keys(mine, &ma, &mb);
+    }
+    int rank = 0;
+    for (int base = 0; base < n; base += 256) {
+        const int q = base + threadIdx.x;
+        __syncthreads();
+        if (q < n) {
+            const SiftOri other = ori[q];
+            sift_keys(other, &sa[threadIdx.x], &sb[threadIdx.x]);
+        }
+        __syncthreads();
+        const int m = min(256, n - base);
+        for (int s = 0; s < m; ++s) rank += (sa[s] < ma || (sa[s] == ma && sb[s] < mb)) ? 1 : 0;
+    }
+    if (t < n) sorted[rank] = mine;
+}
+
+// One wave per kept keypoint k < min(count, cap, K). kp_out [K][4] = x, y, size, response (final coordinates); desc_out [K][128].
+__global__ __launch_bounds__(64) void sift_describe_kernel(const float* __restrict__ pyr, SiftGeom geom, const SiftOri* __restrict__ sorted,
+                                                         const int* __restrict__ counts, int cap, int K, float* __restrict__ kp_out,
+                                                         float* __restrict__ desc_out) {
+    __shared__ float hist[360];
+    __shared__ int s_r0[64], s_c0[64], s_o0[64];
+    __shared__ float s_rb[64], s_cb[64], s_ob[64], s_mag[64];
+    __shared__ float dst[128];
+    __shared__ float s_norm;
+    const int k = blockIdx.x, lane = threadIdx.x;
+    if (k >= min(min(counts[2], cap), K)) return;
+    const SiftOri kp = sorted[k];
+    const SiftOct oc = geom.o[kp.o];
+    const int H = oc.H, W = oc.W;
+    const float* img = pyr + oc.g + (size_t)kp.l * H * W;
+    for (int q = lane; q < 360; q += 64) hist[q] = 0.0f;
+    float ori = 360.0f - kp.angle;
+    if (fabsf(ori - 360.0f) < FLT_EPSILON) ori = 0.0f;
+    const int px = (int)rintf(kp.x), py = (int)rintf(kp.y);
+    float cos_t, sin_t;
+    sift_sincos_deg(ori, &cos_t, &sin_t);
+    const float bins_per_deg = 8.0f / 360.0f;
+    const float exp_scale = -1.0f / (4.0f * 4.0f * 0.5f);
+    const float hist_width = 3.0f * kp.scl;
+    int radius = (int)rintf(hist_width * 1.4142135623730951f * 5.0f * 0.5f);
+    radius = min(radius, oc.diag);
+    cos_t = cos_t / hist_width, sin_t = sin_t / hist_width;
+    const int side = 2 * radius + 1, total = side * side;
+    const int rb = lane / 6, cb = lane % 6;  // the spatial cell lanes 0 .. 35 own
+    for (int base = 0; base < total; base += 64) {
+        const int idx = base + lane;
+        int r0 = -100, c0 = 0, o0 = 0;
+        float rbin = 0.f, cbin = 0.f, obin = 0.f, mag = 0.f;
+        if (idx < total) {
+            const int i = idx / side - radius, j = idx % side - radius;
+            const float c_rot = (float)j * cos_t - (float)i * sin_t, r_rot = (float)j * sin_t + (float)i * cos_t;
+            rbin = r_rot + 2.0f - 0.5f, cbin = c_rot + 2.0f - 0.5f;
+            const int r = py + i, c = px + j;
+            if (rbin > -1.0f && rbin < 4.0f && cbin > -1.0f && cbin < 4.0f && r > 0 && r < H - 1 && c > 0 && c < W - 1) {
+                const float* p = img + (size_t)r * W + c;
+                const float dx = p[1] - p[-1], dy = p[-W] - p[W];
+                const float w = sift_exp((c_rot * c_rot + r_rot * r_rot) * exp_scale);
+                obin = (sift_atan2_deg(dy, dx) - ori) * bins_per_deg;
+                mag = sqrtf(dx * dx + dy * dy) * w;
+                const float fr = floorf(rbin), fc = floorf(cbin), fo = floorf(obin);
+                r0 = (int)fr, c0 = (int)fc, o0 = (int)fo;
+                rbin = rbin - fr, cbin = cbin - fc, obin = obin - fo;
+                if (o0 < 0) o0 += 8;
+                if (o0 >= 8) o0 -= 8;
+            }
+        }
+        __syncthreads();
+        s_r0[lane] = r0, s_c0[lane] = c0, s_o0[lane] = o0;
+        s_rb[lane] = rbin, s_cb[lane] = cbin, s_ob[lane] = obin, s_mag[lane] = mag;
+        __syncthreads();
+        const int m = min(64, total - base);
+        if (lane < 36)
+            for (int s = 0; s < m; ++s) {
+                const int dr = rb - (s_r0[s] + 1), dc = cb - (s_c0[s] + 1);  // r0, c0 in -1 .. 3: cells r0 + 1 and r0 + 2
+                if (dr < 0 || dr > 1 || dc < 0 || dc > 1) continue;
+                const float mg = s_mag[s];
+                const float v_r1 = mg * s_rb[s], v_r0 = mg - v_r1;
+                const float vr = dr ? v_r1 : v_r0;
+                const float v_rc1 = vr * s_cb[s], v_rc0 = vr - v_rc1;
+                const float vrc = dc ? v_rc1 : v_rc0;
+                const float v_o1 = vrc * s_ob[s], v_o0 = vrc - v_o1;
+                const int at = lane * 10 + s_o0[s];  // o0 in 0 .. 7
+                hist[at] = hist[at] + v_o0;
+                hist[at + 1] = hist[at + 1] + v_o1;
+            }
+    }
+    __syncthreads();
+    if (lane < 16) {  // fold the circular orientation bins 8 and 9 onto 0 and 1
+        const int at = ((lane / 4 + 1) * 6 + (lane % 4 + 1)) * 10;
+        hist[at] = hist[at] + hist[at + 8];
+        hist[at + 1] = hist[at + 1] + hist[at + 9];
+    }
+    __syncthreads();
+    for (int q = lane; q < 128; q += 64) {
+        const int cell = q >> 3;
+        dst[q] = hist[((cell / 4 + 1) * 6 + (cell % 4 + 1)) * 10 + (q & 7)];
+    }
+    __syncthreads();
+    if (lane == 0) {
+        float nrm2 = 0.0f;
+        for (int q = 0; q < 128; ++q) nrm2 = nrm2 + dst[q] * dst[q];
+        s_norm = sqrtf(nrm2) * 0.2f;
+    }
+    __syncthreads();
+    const float thr = s_norm;
+    for (int q = lane; q < 128; q += 64) dst[q] = fminf(dst[q], thr);
+    __syncthreads();
+    if (lane == 0) {
+        float nrm2 = 0.0f;
+        for (int q = 0; q < 128; ++q) nrm2 = nrm2 + dst[q] * dst[q];
+        s_norm = 512.0f / fmaxf(sqrtf(nrm2), FLT_EPSILON);
+    }
+    __syncthreads();
+    const float scale = s_norm;
+    for (int q = lane; q < 128; q += 64) desc_out[(size_t)k * 128 + q] = fminf(fmaxf(rintf(dst[q] * scale), 0.0f), 255.0f);
+    if (lane == 0) {
+        float* o = kp_out + (size_t)k * 4;
+        o[0] = ldexpf(kp.x, kp.o - 1), o[1] = ldexpf(kp.y, kp.o - 1), o[2] = ldexpf(kp.scl, kp.o), o[3] = kp.resp;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------------------------------------
+// host
+// ------------------------------------------------------------------------------------------------------------------------------
+const char* sift_shape_error(int B, int H, int W, int cand_cap, int kp_cap) {
+    if (B < 1 || cand_cap < 1 || kp_cap < 1) return "need batch >= 1 and capacities >= 1";
+    if (H < 1 || W < 1) return "need images of at least 1 x 1 pixels";
+    if (2 * (long long)H > SIFT_MAX_EDGE || 2 * (long long)W > SIFT_MAX_EDGE) return "the doubled image exceeds 32767 pixels on an edge";
+    if (cand_cap > (1 << 26) || kp_cap > (1 << 24)) return "capacity exceeds 2^26 candidates or 2^24 keypoints";
+    return nullptr;
+}
+
+int sift_blur(const float* in, float* tmp, float* out, int H, int W, double sigma, hipStream_t st) {
+    const SiftTaps taps = sift_taps(sigma);
+    const dim3 grid(ceil_div(W, 256), H);
+    hipLaunchKernelGGL(sift_blur_row_kernel, grid, dim3(256), 0, st, in, tmp, H, W, taps);
+    GTSFM_CHECK_LAUNCH("sift_blur_row_kernel");
+    hipLaunchKernelGGL(sift_blur_col_kernel, grid, dim3(256), 0, st, tmp, out, H, W, taps);
+    GTSFM_CHECK_LAUNCH("sift_blur_col_kernel");
+    return GTSFM_OK;
+}
+
+#define SIFT_HIP(call, what)                                       \
+    do {                                                           \
+        if ((call) != hipSuccess) {                                \
+            gtsfm_set_error("sift: %s failed", what);              \
+            return GTSFM_ERR_HIP;                                  \
+        }                                                          \
+    } while (0)
+
+// One image through the stages up to `stage` (0 pyramid, 1 candidates, 2 keypoints, 3 oriented and sorted, 4 everything).
+// counts_out [4] int32 on the device: candidates, keypoints and oriented keypoints FOUND, and 0.
+int sift_image(const uint8_t* gray, const uint8_t* mask, int H, int W, const SiftGeom& g, const SiftWs& s, int stage, int K, int cand_cap, int kp_cap,
+               void* out, int32_t* counts_out, float* kp_out, float* desc_out, char* ws, hipStream_t st) {
+    float* pyr = reinterpret_cast<float*>(ws + s.pyr);
+    float* tmpA = reinterpret_cast<float*>(ws + s.tmpA);
+    float* tmpB = reinterpret_cast<float*>(ws + s.tmpB);
+    unsigned* claim = reinterpret_cast<unsigned*>(ws + s.claim);
+    int4* cand = reinterpret_cast<int4*>(ws + s.cand);
+    SiftKp* kps = reinterpret_cast<SiftKp*>(ws + s.kps);
+    SiftOri* ori = reinterpret_cast<SiftOri*>(ws + s.ori);
+    SiftOri* sorted = reinterpret_cast<SiftOri*>(ws + s.sorted);
+    int* counts = reinterpret_cast<int*>(ws + s.counts);
+    SIFT_HIP(hipMemsetAsync(counts, 0, 16, st), "hipMemsetAsync");
+    if (g.n > 0) {
+        hipLaunchKernelGGL(sift_upsample_kernel, dim3(ceil_div(g.W2, 256), g.H2), dim3(256), 0, st, gray, H, W, tmpA);
+        GTSFM_CHECK_LAUNCH("sift_upsample_kernel");
+        for (int o = 0; o < g.n; ++o) {
+            const int h = g.o[o].H, w = g.o[o].W;
+            const size_t plane = (size_t)h * w;
+            float* G = pyr + g.o[o].g;
+            if (o == 0) {
+                const int rc = sift_blur(tmpA, tmpB, G, h, w, sift_layer_sigma(0), st);
+                if (rc) return rc;
+            } else {
+                hipLaunchKernelGGL(sift_decimate_kernel, dim3(ceil_div(w, 256), h), dim3(256), 0, st, pyr + g.o[o - 1].g + 3 * (size_t)g.o[o - 1].H * g.o[o - 1].W,
+                                   g.o[o - 1].W, G, w);
+                GTSFM_CHECK_LAUNCH("sift_decimate_kernel");
+            }
+            for (int i = 1; i < 6; ++i) {
+                const int rc = sift_blur(G + (i - 1) * plane, tmpB, G + i * plane, h, w, sift_layer_sigma(i), st);
+                if (rc) return rc;
+            }
+            const size_t total = 5 * plane;
+            hipLaunchKernelGGL(sift_dog_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, G, pyr + g.o[o].d, plane, total);
+            GTSFM_CHECK_LAUNCH("sift_dog_kernel");
+        }
+    }
+    if (stage == 0) {
+        if (g.floats > 0) SIFT_HIP(hipMemcpyAsync(out, pyr, (size_t)g.floats * 4, hipMemcpyDeviceToDevice, st), "hipMemcpyAsync");
+        return GTSFM_OK;
+    }
+    for (int o = 0; o < g.n; ++o) {
+        const int h = g.o[o].H, w = g.o[o].W;
+        if (h <= 2 * SIFT_BORDER || w <= 2 * SIFT_BORDER) continue;
+        hipLaunchKernelGGL(sift_extrema_kernel, dim3(ceil_div(w - 2 * SIFT_BORDER, 256), h - 2 * SIFT_BORDER, 3), dim3(256), 0, st, pyr + g.o[o].d, h, w, o,
+                           cand_cap, counts, cand);
+        GTSFM_CHECK_LAUNCH("sift_extrema_kernel");
+    }
+    if (stage >= 2) {
+        SIFT_HIP(hipMemsetAsync(claim, 0, (size_t)g.claim_words * 4 + 4, st), "hipMemsetAsync");
+        hipLaunchKernelGGL(sift_refine_kernel, dim3(ceil_div(cand_cap, 256)), dim3(256), 0, st, pyr, g, cand, cand_cap, kp_cap, counts, claim, kps);
+        GTSFM_CHECK_LAUNCH("sift_refine_kernel");
+    }
+    if (stage >= 3) {
+        hipLaunchKernelGGL(sift_orient_kernel, dim3(kp_cap), dim3(64), 0, st, pyr, g, kps, kp_cap, mask, H, W, counts, ori);
+        GTSFM_CHECK_LAUNCH("sift_orient_kernel");
+        hipLaunchKernelGGL(sift_rank_kernel, dim3(ceil_div(kp_cap, 256)), dim3(256), 0, st, ori, counts, kp_cap, sorted);
+        GTSFM_CHECK_LAUNCH("sift_rank_kernel");
+    }
+    if (stage >= 4) {
+        hipLaunchKernelGGL(sift_describe_kernel, dim3(K), dim3(64), 0, st, pyr, g, sorted, counts, kp_cap, K, kp_out, desc_out);
+        GTSFM_CHECK_LAUNCH("sift_describe_kernel");
+    }
+    if (stage == 1) SIFT_HIP(hipMemcpyAsync(out, cand, (size_t)cand_cap * 16, hipMemcpyDeviceToDevice, st), "hipMemcpyAsync");
+    if (stage == 2) SIFT_HIP(hipMemcpyAsync(out, kps, (size_t)kp_cap * sizeof(SiftKp), hipMemcpyDeviceToDevice, st), "hipMemcpyAsync");
+    if (stage == 3) SIFT_HIP(hipMemcpyAsync(out, sorted, (size_t)kp_cap * sizeof(SiftOri), hipMemcpyDeviceToDevice, st), "hipMemcpyAsync");
+    SIFT_HIP(hipMemcpyAsync(counts_out, counts, 16, hipMemcpyDeviceToDevice, st), "hipMemcpyAsync");
+    return GTSFM_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int gtsfm_sift_num_octaves(int height, int width) {
+    if (height < 1 || width < 1 || 2LL * height > SIFT_MAX_EDGE || 2LL * width > SIFT_MAX_EDGE) return 0;
+    return sift_geometry(height, width).n;
+}
+
+size_t gtsfm_sift_pyramid_floats(int height, int width) {
+    if (height < 1 || width < 1 || 2LL * height > SIFT_MAX_EDGE || 2LL * width > SIFT_MAX_EDGE) return 0;
+    return (size_t)sift_geometry(height, width).floats;
+}
+
+size_t gtsfm_sift_workspace_bytes(int batch, int height, int width, int cand_capacity, int kp_capacity) {
+    const char* why = sift_shape_error(batch, height, width, cand_capacity, kp_capacity);
+    if (why) {
+        gtsfm_set_error("sift: %s (got %d x %d x %d, capacities %d / %d)", why, batch, height, width, cand_capacity, kp_capacity);
+        return 0;
+    }
+    return sift_ws(sift_geometry(height, width), cand_capacity, kp_capacity).total;
+}
+
+int gtsfm_sift_detect_and_describe(const uint8_t* gray_dev, const uint8_t* mask_dev, int batch, int height, int width, int max_keypoints, int cand_capacity,
+                                   int kp_capacity, int32_t* counts_dev, float* keypoints_dev, float* desc_dev, void* workspace_dev, size_t workspace_bytes,
+                                   void* stream) {
+    GTSFM_CHECK_ARG(gray_dev && counts_dev && keypoints_dev && desc_dev && workspace_dev, "sift_detect_and_describe: null pointer");
+    GTSFM_CHECK_ARG(max_keypoints >= 1, "sift_detect_and_describe: max_keypoints must be positive (got %d)", max_keypoints);
+    const char* why = sift_shape_error(batch, height, width, cand_capacity, kp_capacity);
+    GTSFM_CHECK_ARG(!why, "sift: %s (got %d x %d x %d, capacities %d / %d)", why, batch, height, width, cand_capacity, kp_capacity);
+    const SiftGeom g = sift_geometry(height, width);
+    const SiftWs s = sift_ws(g, cand_capacity, kp_capacity);
+    GTSFM_CHECK_ARG(workspace_bytes >= s.total, "sift: workspace too small (%zu < %zu bytes)", workspace_bytes, s.total);
+    hipStream_t st = (hipStream_t)stream;
+    const size_t px = (size_t)height * width;
+    for (int b = 0; b < batch; ++b) {
+        const int rc = sift_image(gray_dev + b * px, mask_dev ? mask_dev + b * px : nullptr, height, width, g, s, 4, max_keypoints, cand_capacity, kp_capacity,
+                                  nullptr, counts_dev + 4 * b, keypoints_dev + (size_t)b * max_keypoints * 4, desc_dev + (size_t)b * max_keypoints * 128,
+                                  reinterpret_cast<char*>(workspace_dev), st);
+        if (rc) return rc;
+    }
+    int32_t found[4 * 64];
+    for (int b0 = 0; b0 < batch; b0 += 64) {  // an overflow is an error, never a silent truncation
+        const int nb = batch - b0 < 64 ? batch - b0 : 64;
+        SIFT_HIP(hipMemcpyAsync(found, counts_dev + 4 * b0, (size_t)nb * 16, hipMemcpyDeviceToHost, st), "hipMemcpyAsync");
+        SIFT_HIP(hipStreamSynchronize(st), "hipStreamSynchronize");
+        for (int b = 0; b < nb; ++b) {
+            const int32_t* f = found + 4 * b;
+            if (f[0] > cand_capacity || f[1] > kp_capacity || f[2] > kp_capacity) {
+                gtsfm_set_error("sift: image %d has %d candidates / %d keypoints / %d oriented keypoints, above the capacities %d / %d: repeat with larger ones",
+                                b0 + b, f[0], f[1], f[2], cand_capacity, kp_capacity);
+                return GTSFM_ERR_WORKSPACE;
+            }
+        }
+    }
+    return GTSFM_OK;
+}
+
+int gtsfm_sift_stage(const uint8_t* gray_dev, const uint8_t* mask_dev, int height, int width, int stage, int cand_capacity, int kp_capacity, void* out_dev,
+                     int32_t* counts_dev, void* workspace_dev, size_t workspace_bytes, void* stream) {
+    GTSFM_CHECK_ARG(gray_dev && out_dev && counts_dev && workspace_dev, "sift_stage: null pointer");
+    GTSFM_CHECK_ARG(stage >= 0 && stage <= 3, "sift_stage: stage must be 0, 1, 2 or 3 (got %d)", stage);
+    const char* why = sift_shape_error(1, height, width, cand_capacity, kp_capacity);
+    GTSFM_CHECK_ARG(!why, "sift: %s (got %d x %d, capacities %d / %d)", why, height, width, cand_capacity, kp_capacity);
+    const SiftGeom g = sift_geometry(height, width);
+    const SiftWs s = sift_ws(g, cand_capacity, kp_capacity);
+    GTSFM_CHECK_ARG(workspace_bytes >= s.total, "sift: workspace too small (%zu < %zu bytes)", workspace_bytes, s.total);
+    return sift_image(gray_dev, mask_dev, height, width, g, s, stage, 0, cand_capacity, kp_capacity, out_dev, counts_dev, nullptr, nullptr,
+                      reinterpret_cast<char*>(workspace_dev), (hipStream_t)stream);
+}
+
+}  // extern "C"

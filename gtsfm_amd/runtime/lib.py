@@ -226,6 +226,18 @@ SIGNATURES = {
         [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
          C.c_void_p],
     ),
+    "gtsfm_sift_num_octaves": (C.c_int, [C.c_int, C.c_int]),
+    "gtsfm_sift_pyramid_floats": (C.c_size_t, [C.c_int, C.c_int]),
+    "gtsfm_sift_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "gtsfm_sift_detect_and_describe": (
+        C.c_int,
+        [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
+         C.c_void_p],
+    ),
+    "gtsfm_sift_stage": (
+        C.c_int,
+        [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p],
+    ),
 }
 
 

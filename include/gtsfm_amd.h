@@ -560,6 +560,47 @@ int gtsfm_d2net_detect(const float* map_dev, int batch, int map_height, int map_
                        void* candidates_dev, float* keypoints_dev, float* scores_dev, float* desc_dev, void* workspace_dev, size_t workspace_bytes,
                        void* stream);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * SIFT detector-descriptor, OpenCV's SIFT_create() defaults
+ *   SG = gtsfm/frontend/detector_descriptor/sift.py (cv.SIFT_create().detectAndCompute + Keypoints.get_top_k)
+ * nOctaveLayers 3, contrastThreshold 0.04, edgeThreshold 10, sigma 1.6, float32 pyramid, first octave -1 (the image is doubled).
+ * The pyramid of a height x width image has n = round(log2(min(2 height, 2 width))) - 2 octaves; octave o is (2 height >> o) x
+ * (2 width >> o). Its layout in floats: the six Gaussian images of octave 0, of octave 1, ..., then the five DoG images of octave 0, ...
+ * Records (32-bit words): a candidate is int32 octave, layer, row, column; a keypoint is those four, then float x = column + X0,
+ * y = row + X1 (octave coordinates), scl = 1.6 * 2^((layer + X2) / 3), response; an oriented keypoint is a keypoint followed by float
+ * angle (degrees) and a zero word. Final coordinates: (x, y) * 2^(octave - 1), size = scl * 2^octave.
+ * tests/sift_reference.py restates every stage in numpy in the same operation order; the device equals it bit for bit.
+ * ---------------------------------------------------------------------------------------------------------- */
+
+/* Octaves and floats of the pyramid (0 for a shape the calls refuse). */
+int gtsfm_sift_num_octaves(int height, int width);
+size_t gtsfm_sift_pyramid_floats(int height, int width);
+
+/* Bytes of device workspace a call needs (0 for a shape the calls refuse, with the reason in gtsfm_last_error: batch >= 1, both
+ * edges in 1 .. 16383, cand_capacity in 1 .. 2^26, kp_capacity in 1 .. 2^24). The workspace holds ONE image's pyramid: a batch runs
+ * image after image on the stream. cand_capacity: candidate records; kp_capacity: keypoint and oriented-keypoint records. */
+size_t gtsfm_sift_workspace_bytes(int batch, int height, int width, int cand_capacity, int kp_capacity);
+
+/* detectAndCompute + top-k for a batch of equally-sized gray images.                                         replaces SG:41-54
+ * gray_dev [batch][height][width] uint8; mask_dev the same shape or NULL: a keypoint whose mask[round(y)][round(x)] is 0 is dropped
+ * before the top-k. The first min(counts_dev[4 b + 2], max_keypoints) rows of image b are written, ordered by response descending,
+ * equal responses by (octave, layer, row, column, angle) ascending (OpenCV and get_top_k promise no order):
+ * keypoints_dev [batch][max_keypoints][4] = x, y, size, response; desc_dev [batch][max_keypoints][128] float32 holding the integers
+ * 0 .. 255 that cv2 returns.
+ * counts_dev [batch][4] int32: candidates, keypoints and oriented keypoints FOUND, and 0. The call waits for the stream; when a
+ * count exceeds its capacity it returns GTSFM_ERR_WORKSPACE with the counts in gtsfm_last_error and that image's outputs are
+ * incomplete: repeat with at least those capacities. Per image, the result does not depend on the batch or on the run. */
+int gtsfm_sift_detect_and_describe(const uint8_t* gray_dev, const uint8_t* mask_dev, int batch, int height, int width, int max_keypoints, int cand_capacity,
+                                   int kp_capacity, int32_t* counts_dev, float* keypoints_dev, float* desc_dev, void* workspace_dev, size_t workspace_bytes,
+                                   void* stream);
+
+/* The stages of one image (same kernels), for stage-wise tests and timing; the call does not wait. stage 0: the pyramid,
+ * out_dev [gtsfm_sift_pyramid_floats] float32; 1: candidates, out_dev [cand_capacity] records in any order; 2: keypoints,
+ * out_dev [kp_capacity] records in any order; 3: oriented keypoints after the mask, out_dev [kp_capacity] records in the output
+ * order. counts_dev [4] as above (stages >= 1); of every list the first min(count, capacity) records are written. */
+int gtsfm_sift_stage(const uint8_t* gray_dev, const uint8_t* mask_dev, int height, int width, int stage, int cand_capacity, int kp_capacity, void* out_dev,
+                     int32_t* counts_dev, void* workspace_dev, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
