@@ -148,10 +148,10 @@ class D2NetEngine:
             host = np.stack([normalise(im if im.ndim == 3 else np.repeat(im[:, :, np.newaxis], 3, -1)) for im in images])
         return torch.from_numpy(host).to(self.device), layout, len(images), h, w
 
-    def detect_batch(self, images: Sequence[np.ndarray], max_keypoints: int = 5000, cand_capacity: int = 0) -> List[Tuple[np.ndarray, np.ndarray, np.ndarray]]:
-        """Per image ``(keypoints (N, 2) float32 (x, y), scores (N,) float32, descriptors (N, 512) float32)``, N <= max_keypoints, by
-        score descending (equal scores by channel, row, column). ``cand_capacity``: records per image of the candidate list (default
-        2 x the map's pixels); when an image has more candidates the call is repeated with the reported count."""
+    def _detect_device(self, images: Sequence[np.ndarray], max_keypoints: int, cand_capacity: int = 0):
+        """One batch of equal-sized images through ``gtsfm_d2net_forward``, repeated while the candidate list is too small. Returns
+        ``(found [B] host counts, k, keypoints [B][k][2], scores [B][k], descriptors [B][k][512])``; image i's first
+        ``min(found[i], k)`` rows are valid."""
         torch = self._torch
         if max_keypoints < 1:
             raise ValueError(f"max_keypoints must be positive (got {max_keypoints})")
@@ -170,14 +170,49 @@ class D2NetEngine:
             self._L.check(rc, "gtsfm_d2net_forward")
             found = counts.cpu().numpy()
             if int(found.max()) <= cap:
-                break
+                return found, k, kp, sc, de
             cap = int(found.max())  # the list was too small for at least one image: repeat, never truncate
             self.relaunches += 1
+
+    def detect_batch(self, images: Sequence[np.ndarray], max_keypoints: int = 5000, cand_capacity: int = 0) -> List[Tuple[np.ndarray, np.ndarray, np.ndarray]]:
+        """Per image ``(keypoints (N, 2) float32 (x, y), scores (N,) float32, descriptors (N, 512) float32)``, N <= max_keypoints, by
+        score descending (equal scores by channel, row, column). ``cand_capacity``: records per image of the candidate list (default
+        2 x the map's pixels); when an image has more candidates the call is repeated with the reported count."""
+        found, k, kp, sc, de = self._detect_device(images, max_keypoints, cand_capacity)
         out = []
-        for i in range(b):
+        for i in range(len(found)):
             n = min(int(found[i]), k)
             out.append((kp[i, :n].cpu().numpy(), sc[i, :n].cpu().numpy(), de[i, :n].cpu().numpy()))
         return out
+
+    def detect_table(self, images: Sequence[np.ndarray], max_keypoints: int = 5000, image_batch: int = 8) -> Dict[str, object]:
+        """Images of any mix of shapes -> one device-resident feature table with ``cap = max_keypoints`` rows per image: ``xy``
+        [n][cap][2], ``responses`` [n][cap], ``descriptors`` [n][cap][512] float32, ``count`` [n] int32. The images are grouped by shape
+        (and dtype) and go through ``detect_batch``'s call in groups of at most ``image_batch``; image i's first ``count[i]`` rows are
+        byte for byte what ``detect_batch`` returns for it. Rows beyond the count are zero."""
+        torch = self._torch
+        if image_batch < 1:
+            raise ValueError(f"image_batch must be positive (got {image_batch})")
+        images = [np.asarray(im) for im in images]
+        n, cap = len(images), int(max_keypoints)
+        if cap < 1:
+            raise ValueError(f"max_keypoints must be positive (got {max_keypoints})")
+        xy = torch.zeros((n, cap, 2), dtype=torch.float32, device=self.device)
+        resp = torch.zeros((n, cap), dtype=torch.float32, device=self.device)
+        desc = torch.zeros((n, cap, DESCRIPTOR_DIM), dtype=torch.float32, device=self.device)
+        count = np.zeros(n, dtype=np.int32)
+        groups: Dict[Tuple[object, ...], List[int]] = {}
+        for i, im in enumerate(images):
+            groups.setdefault((tuple(im.shape), im.dtype.str), []).append(i)
+        for members in groups.values():
+            for g0 in range(0, len(members), image_batch):
+                ids = members[g0 : g0 + image_batch]
+                found, k, kp, sc, de = self._detect_device([images[i] for i in ids], cap)
+                for b, i in enumerate(ids):
+                    c = min(int(found[b]), k)
+                    count[i] = c
+                    xy[i, :c], resp[i, :c], desc[i, :c] = kp[b, :c], sc[b, :c], de[b, :c]
+        return {"xy": xy, "responses": resp, "descriptors": desc, "count": torch.from_numpy(count).to(self.device), "count_host": count}
 
     def detect(self, image: np.ndarray, max_keypoints: int = 5000, cand_capacity: int = 0) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
         return self.detect_batch([image], max_keypoints, cand_capacity)[0]

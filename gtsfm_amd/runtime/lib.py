@@ -174,6 +174,8 @@ SIGNATURES = {
         [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_double, C.c_void_p, C.c_size_t, C.c_void_p,
          C.c_void_p, C.c_void_p],
     ),
+    "gtsfm_twoway_order_matches": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gtsfm_pack_rows_f32_to_u8": (C.c_int, [C.c_void_p, C.c_longlong, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "gtsfm_netvlad_packed_weight_floats": (C.c_size_t, [C.c_int]),
     "gtsfm_netvlad_pack_weights": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.c_void_p]),
     "gtsfm_netvlad_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),

@@ -103,11 +103,9 @@ class SiftEngine:
             raise ValueError("one mask (or None) per image")
         return self._torch.from_numpy(np.stack(rows)).to(self.device)
 
-    def detect_batch(self, images: Sequence[np.ndarray], max_keypoints: int = 5000, masks: Optional[Sequence[Optional[np.ndarray]]] = None,
-                     cand_capacity: int = 0, kp_capacity: int = 0) -> List[Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray]]:
-        """Per image ``(coordinates (N, 2) (x, y), sizes (N,), responses (N,), descriptors (N, 128))``, float32, N <= max_keypoints, by
-        response descending (equal responses by octave, layer, row, column, angle). A keypoint whose mask pixel is 0 is dropped before
-        the top-k. When an image has more candidates or keypoints than the lists hold, the call is repeated with what it reported."""
+    def _detect_device(self, images, max_keypoints: int, masks, cand_capacity: int = 0, kp_capacity: int = 0):
+        """One batch of equal-sized images through ``gtsfm_sift_detect_and_describe``, repeated while a list is too small. Returns
+        ``(found [B][4] host counts, k, out_kp [B][k][4], out_de [B][k][128])``; image i's first ``min(found[i, 2], k)`` rows are valid."""
         torch = self._torch
         if max_keypoints < 1:
             raise ValueError(f"max_keypoints must be positive (got {max_keypoints})")
@@ -130,13 +128,62 @@ class SiftEngine:
                 self.relaunches += 1
                 continue
             self._L.check(rc, "gtsfm_sift_detect_and_describe")
-            break
+            return found, k, out_kp, out_de
+
+    def detect_batch(self, images: Sequence[np.ndarray], max_keypoints: int = 5000, masks: Optional[Sequence[Optional[np.ndarray]]] = None,
+                     cand_capacity: int = 0, kp_capacity: int = 0) -> List[Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray]]:
+        """Per image ``(coordinates (N, 2) (x, y), sizes (N,), responses (N,), descriptors (N, 128))``, float32, N <= max_keypoints, by
+        response descending (equal responses by octave, layer, row, column, angle). A keypoint whose mask pixel is 0 is dropped before
+        the top-k. When an image has more candidates or keypoints than the lists hold, the call is repeated with what it reported."""
+        found, k, out_kp, out_de = self._detect_device(images, max_keypoints, masks, cand_capacity, kp_capacity)
         out = []
-        for i in range(b):
+        for i in range(len(found)):
             n = min(int(found[i, 2]), k)
             rows = out_kp[i, :n].cpu().numpy()
             out.append((rows[:, :2].copy(), rows[:, 2].copy(), rows[:, 3].copy(), out_de[i, :n].cpu().numpy()))
         return out
+
+    def detect_table(self, images: Sequence[np.ndarray], max_keypoints: int = 5000, masks: Optional[Sequence[Optional[np.ndarray]]] = None,
+                     image_batch: int = 8) -> Dict[str, object]:
+        """Images of any mix of shapes -> one device-resident feature table with ``cap = max_keypoints`` rows per image: ``xy``
+        [n][cap][2], ``sizes`` [n][cap], ``responses`` [n][cap] float32, ``descriptors`` [n][cap][128] uint8, ``count`` [n] int32. The
+        images are grouped by shape and go through ``detect_batch``'s call in groups of at most ``image_batch``; image i's first
+        ``count[i]`` rows are what ``detect_batch`` returns for it (the descriptors after the cast: a value that is not an integer in
+        0 .. 255 raises ``RuntimeError``, nothing is clamped). Rows beyond the count are zero."""
+        torch = self._torch
+        if image_batch < 1:
+            raise ValueError(f"image_batch must be positive (got {image_batch})")
+        images = [np.asarray(im) for im in images]
+        masks = [None] * len(images) if masks is None else list(masks)
+        if len(masks) != len(images):
+            raise ValueError("one mask (or None) per image")
+        n, cap = len(images), int(max_keypoints)
+        if cap < 1:
+            raise ValueError(f"max_keypoints must be positive (got {max_keypoints})")
+        rows = torch.zeros((n, cap, 4), dtype=torch.float32, device=self.device)
+        desc = torch.zeros((n, cap, DESCRIPTOR_DIM), dtype=torch.uint8, device=self.device)
+        count = np.zeros(n, dtype=np.int32)
+        flag = torch.zeros(1, dtype=torch.int32, device=self.device)
+        groups: Dict[Tuple[int, ...], List[int]] = {}
+        for i, im in enumerate(images):
+            groups.setdefault(tuple(im.shape), []).append(i)
+        for members in groups.values():
+            for g0 in range(0, len(members), image_batch):
+                ids = members[g0 : g0 + image_batch]
+                found, k, out_kp, out_de = self._detect_device([images[i] for i in ids], cap, [masks[i] for i in ids])
+                for b, i in enumerate(ids):
+                    c = min(int(found[b, 2]), k)
+                    count[i] = c
+                    if c == 0:
+                        continue
+                    rows[i, :c] = out_kp[b, :c]
+                    rc = self._lib.gtsfm_pack_rows_f32_to_u8(out_de[b].data_ptr(), c, DESCRIPTOR_DIM, DESCRIPTOR_DIM, desc[i].data_ptr(), DESCRIPTOR_DIM,
+                                                             flag.data_ptr(), self._L.current_stream_handle())
+                    self._L.check(rc, "gtsfm_pack_rows_f32_to_u8")
+        if n and int(flag.cpu()[0]) != 0:
+            raise RuntimeError("a SIFT descriptor value is not an integer in 0 .. 255: the uint8 table cannot hold it")
+        return {"xy": rows[:, :, :2].contiguous(), "sizes": rows[:, :, 2].contiguous(), "responses": rows[:, :, 3].contiguous(), "descriptors": desc,
+                "count": torch.from_numpy(count).to(self.device), "count_host": count}
 
     def detect(self, image: np.ndarray, max_keypoints: int = 5000, mask: Optional[np.ndarray] = None, cand_capacity: int = 0,
                kp_capacity: int = 0) -> Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray]:

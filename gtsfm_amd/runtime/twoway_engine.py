@@ -131,3 +131,69 @@ class TwoWayEngine:
                 out[(i1, i2)] = kept_in_distance_order(m_h[start : start + n1], d_h[start : start + n1])
                 start += n1
         return {(int(i1), int(i2)): out[(i1, i2)] for i1, i2 in pairs}
+
+    def order_matches(self, matches0, dist0, blk_off, num_pairs: int, match_idx, match_count) -> None:
+        """``gtsfm_twoway_order_matches`` on device tensors: ``blk_off`` int64 [num_pairs + 1] row offsets into ``matches0`` / ``dist0``
+        and ``match_idx`` [rows][2] int32; ``match_count`` int32 [num_pairs]. Enqueued on the current stream."""
+        torch = self._torch
+        if (matches0.dtype != torch.int32 or dist0.dtype != torch.float32 or blk_off.dtype != torch.int64 or match_idx.dtype != torch.int32
+                or match_count.dtype != torch.int32 or blk_off.numel() < num_pairs + 1 or match_count.numel() < num_pairs
+                or not (matches0.is_contiguous() and dist0.is_contiguous() and blk_off.is_contiguous() and match_idx.is_contiguous() and match_count.is_contiguous())):
+            raise TypeError("order_matches needs contiguous int32 matches0 / match_idx / match_count, float32 dist0 and int64 offsets")
+        rc = self._lib.gtsfm_twoway_order_matches(matches0.data_ptr(), dist0.data_ptr(), blk_off.data_ptr(), int(num_pairs), match_idx.data_ptr(),
+                                                  match_count.data_ptr(), self._L.current_stream_handle())
+        self._L.check(rc, "gtsfm_twoway_order_matches")
+
+    def match_table_device(self, desc_table, counts: Sequence[int], pairs: Sequence[Tuple[int, int]], metric: int = EUCLIDEAN,
+                           ratio: Optional[float] = None, pair_batch: int = 32) -> Dict[str, object]:
+        """``match_table`` with the match lists left on the device, in the contract's order: the edges with two non-empty sides go through
+        ``match_raw`` in launches of at most ``pair_batch`` pairs, and ``gtsfm_twoway_order_matches`` writes each launch's kept rows, by
+        distance (ties by row), into one scene-wide ``match_idx`` [sum n1][2] int32 in capacity layout (edge p owns rows
+        ``match_off[p] .. match_off[p + 1]``, the first ``match_count[p]`` of them are matches) -- what ``VerifierEngine.verify_batch``
+        reads. Returns ``pairs`` (the edges matched, in order), ``empty`` (edges with an empty side), ``match_idx``, ``match_off`` (host
+        list), ``match_count`` (device). Nothing is copied to the host."""
+        torch = self._torch
+        if pair_batch < 1:
+            raise ValueError(f"pair_batch must be positive (got {pair_batch})")
+        n_img, cap, dim = desc_table.shape
+        table = desc_table.reshape(n_img * cap, dim)
+        todo: List[Tuple[int, int]] = []
+        empty: List[Tuple[int, int]] = []
+        for i1, i2 in pairs:
+            n1, n2 = int(counts[i1]), int(counts[i2])
+            if n1 == 0 or n2 == 0:
+                empty.append((int(i1), int(i2)))
+            else:
+                check_ratio_sizes(n1, n2, ratio)
+                todo.append((int(i1), int(i2)))
+        n1s = np.array([int(counts[i1]) for i1, _ in todo], dtype=np.int64)
+        match_off = np.concatenate([[0], np.cumsum(n1s)]).astype(np.int64)
+        match_idx = torch.empty((int(match_off[-1]), 2), dtype=torch.int32, device=self.device)
+        match_count = torch.zeros(len(todo), dtype=torch.int32, device=self.device)
+        # every launch's block offsets (relative to the launch's first row) in one upload: chunk c reads blk[c0 + c : c0 + c + len + 1]
+        chunks = [(c0, min(c0 + pair_batch, len(todo))) for c0 in range(0, len(todo), pair_batch)]
+        blk_host = np.concatenate([match_off[a : b + 1] - match_off[a] for a, b in chunks]) if chunks else np.zeros(0, dtype=np.int64)
+        blk = torch.from_numpy(np.ascontiguousarray(blk_host, dtype=np.int64)).to(self.device)
+        for c, (a, b) in enumerate(chunks):
+            spec = [(i1 * cap, int(counts[i1]), i2 * cap, int(counts[i2])) for i1, i2 in todo[a:b]]
+            matches0, dist0 = self.match_raw(table, dim, spec, metric, ratio)
+            self.order_matches(matches0, dist0, blk[a + c : b + c + 1], b - a, match_idx[int(match_off[a]) :], match_count[a:b])
+        return {"pairs": todo, "empty": empty, "match_idx": match_idx, "match_off": match_off.tolist(), "match_count": match_count}
+
+    def matches_to_numpy(self, matched: Dict[str, object]) -> Dict[Tuple[int, int], np.ndarray]:
+        """``match_table_device``'s result -> per edge what ``match_pair`` returns: (K, 2) uint32, or ``np.array([])`` when nothing is
+        kept or a side is empty. Only the first ``match_count`` rows of each edge are copied to the host."""
+        torch = self._torch
+        out: Dict[Tuple[int, int], np.ndarray] = {p: np.array([]) for p in matched["empty"]}
+        pairs = matched["pairs"]
+        if pairs:
+            off = torch.tensor(matched["match_off"], dtype=torch.int64, device=self.device)
+            owner = torch.repeat_interleave(torch.arange(len(pairs), device=self.device), off[1:] - off[:-1])
+            within = torch.arange(int(matched["match_off"][-1]), device=self.device) - off[owner]
+            kept = matched["match_idx"][within < matched["match_count"].to(torch.int64)[owner]].cpu().numpy()
+            count = matched["match_count"].cpu().numpy()
+            start = 0
+            for p, k in zip(pairs, count):
+                out[p] = kept[start : start + int(k)].astype(np.uint32) if k else np.array([])
+                start += int(k)
+        return out

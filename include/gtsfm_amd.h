@@ -411,6 +411,25 @@ int gtsfm_twoway_match(const void* desc_dev, int desc_is_u8, int metric, int dim
                        int use_ratio, double ratio, void* workspace_dev, size_t workspace_bytes, int32_t* matches0_dev, float* dist0_dev,
                        void* stream);
 
+/* gtsfm_twoway_match output -> the verifier's match lists, in the TwoWayMatcher contract's order, on the device.
+ *                                  replaces the stable sort by distance of gtsfm/frontend/matcher/twoway_matcher.py:117-147 and the
+ *                                  host marshalling between the matcher and the verifier.
+ * Pair p owns rows blk_off_dev[p] .. blk_off_dev[p+1] of matches0_dev / dist0_dev (n1 of the pair) and the same rows of
+ * match_idx_dev (capacity layout, as gtsfm_verify_compact_matches fills it). Writes the K_p pairs (i, matches0[i]) with
+ * matches0[i] >= 0, ordered by (dist0[i] ascending as float32, i ascending), to match_idx_dev + 2 * blk_off_dev[p], and K_p to
+ * match_count_dev[p]. Rows beyond K_p are not written. Kept rows must hold a distance >= 0 that is not NaN (what gtsfm_twoway_match
+ * writes). Rank by counting over 64-bit integer keys: no workspace, no host synchronisation, no floating-point reduction, the
+ * same bytes on every run; any n1 (the cost grows with n1^2). At most 65535 pairs per call. */
+int gtsfm_twoway_order_matches(const int32_t* matches0_dev, const float* dist0_dev, const long long* blk_off_dev, int num_pairs,
+                               int32_t* match_idx_dev, int32_t* match_count_dev, void* stream);
+
+/* float32 rows holding integers 0 .. 255 (SIFT descriptors as OpenCV emits them) -> uint8 rows, for a device-resident descriptor
+ * table that gtsfm_twoway_match reads with desc_is_u8 = 1. Row r: src_dev + r * src_stride floats -> dst_dev + r * dst_stride bytes,
+ * `dim` values each. A value that is not an integer in 0 .. 255 (NaN included) is written as 0 and sets *flag_dev to 1; the call
+ * never clears the flag, and nothing is clamped or rounded. */
+int gtsfm_pack_rows_f32_to_u8(const float* src_dev, long long rows, int dim, int src_stride, uint8_t* dst_dev, int dst_stride,
+                              int32_t* flag_dev, void* stream);
+
 /* ------------------------------------------------------------------------------------------------------------
  * NetVLAD global descriptor and similarity retrieval
  *   NV = thirdparty/hloc/netvlad.py, SR = gtsfm/retriever/similarity_retriever.py
