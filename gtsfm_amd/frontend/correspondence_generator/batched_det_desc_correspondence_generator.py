@@ -22,6 +22,7 @@ import numpy as np
 
 from gtsfm_amd.common.keypoints import Keypoints
 from gtsfm_amd.frontend.correspondence_generator.correspondence_generator_base import CorrespondenceGeneratorBase
+from gtsfm_amd.frontend.correspondence_generator.verified_scene import VerifiedScene
 from gtsfm_amd.frontend.detector_descriptor.superpoint import SuperPointDetectorDescriptor
 from gtsfm_amd.frontend.matcher.lightglue_matcher import LightGlueMatcher
 from gtsfm_amd.frontend.matcher.matcher_base import MatcherBase
@@ -72,6 +73,12 @@ class BatchedDetDescCorrespondenceGenerator(CorrespondenceGeneratorBase):
         ``camera_intrinsics``: one calibration per image. Returns the keypoints, the putative correspondences and, per edge, the
         verifier's return tuple ``(i2Ri1, i2Ui1, v_corr_idxs, inlier_ratio_est_model)``; edge (i1, i2) draws its samples from the
         seed ``i1 << 32 | i2``. Calibrations with lens distortion or skew fall back to the per-pair plugin call for their edges."""
+        return self.generate_verified_scene(client, images, visibility_graph, camera_intrinsics, verifier).as_tuple()
+
+    def generate_verified_scene(self, client: Any, images: List[Any], visibility_graph: List[Tuple[int, int]], camera_intrinsics: List[Any],
+                                verifier: Any) -> VerifiedScene:
+        """``generate_correspondences_and_verify`` that also keeps the handles of what stayed in HBM: the returned ``VerifiedScene`` holds
+        the same three objects and builds the scene's feature tracks on the device (``.tracks()`` / ``.tracks_2d()``)."""
         from gtsfm_amd.common.calibration import pinhole_parameters
         from gtsfm_amd.frontend.verifier.ransac import Ransac, _to_pose_types
 
@@ -92,6 +99,7 @@ class BatchedDetDescCorrespondenceGenerator(CorrespondenceGeneratorBase):
             # and stay out of the device batch (a chunk holding such an edge goes to the host as a whole: its match lists are
             # interleaved on the device)
             on_device = [r for r in on_device if all(params[i][4] and params[j][4] for i, j in r["pairs"])]
+        ver: List[Dict[str, Any]] = []
         if on_device:
             intr = np.array([p[:4] for p in params], dtype=np.float64)
             ver = state["pipe"].verify(state["feats"], on_device, intr, float(verifier._estimation_threshold_px), use_intrinsics=use_intrinsics)
@@ -102,13 +110,15 @@ class BatchedDetDescCorrespondenceGenerator(CorrespondenceGeneratorBase):
                 else:
                     rot, direction = _to_pose_types(res["R"], res["t"])
                     verified[pair] = (rot, direction, res["v_corr_idxs"].astype(dtype), res["inlier_ratio"])
+        extra: Dict[Tuple[int, int], np.ndarray] = {}
         for pair in putative:
             if pair not in verified:  # empty keypoint sets, or a calibration the device path does not model
                 i1, i2 = pair
                 per_pair = Ransac(use_intrinsics, verifier._estimation_threshold_px, seed=(i1 << 32) | i2)
                 per_pair._engine = verifier._ensure_engine()  # one lib handle / workspace for every fallback edge
                 verified[pair] = per_pair.verify(keypoints_list[i1], keypoints_list[i2], putative[pair], camera_intrinsics[i1], camera_intrinsics[i2])
-        return keypoints_list, putative, {p: verified[p] for p in putative}
+                extra[pair] = verified[pair][2]
+        return VerifiedScene(keypoints_list, putative, {p: verified[p] for p in putative}, state["feats"], ver, extra)
 
     def _detect_and_match(self, client: Any, images: List[Any], visibility_graph: List[Tuple[int, int]]):
         from gtsfm_amd.runtime.pipeline import FrontEndPipeline

@@ -620,6 +620,40 @@ int gtsfm_sift_detect_and_describe(const uint8_t* gray_dev, const uint8_t* mask_
 int gtsfm_sift_stage(const uint8_t* gray_dev, const uint8_t* mask_dev, int height, int width, int stage, int cand_capacity, int kp_capacity, void* out_dev,
                      int32_t* counts_dev, void* workspace_dev, size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * Feature tracks: union-find over verified matches
+ *   replaces gtsfm/data_association/dsf_tracks_estimator.py:51-85, cpp_dsf_tracks_estimator.py:63-84 (gtsam's DSFMapIndexPair /
+ *   tracksFromPairwiseMatches), called twice per scene from gtsfm/multi_view_optimizer.py:185,199,266-268.
+ * A node is a keypoint: node = node_off[image] + k (in the generators' capacity layout node_off[image] = image * capacity). An edge is
+ * a match row (k1, k2) of pair (i1, i2); i1 == i2 is legal. A row is ACTIVE when its pair is enabled, it lies below match_count[p]
+ * (when counts are given) and mask[row] != 0 (when a mask is given). Every connected component of the active edges is a track, unless
+ * it holds two keypoints of one image: those are counted as discarded (the reference's validate_unique_cameras).
+ * The result depends on the SET of active edges only: not on the order of pairs or rows, on duplicates, or on the run.
+ * ---------------------------------------------------------------------------------------------------------- */
+
+/* Bytes of device workspace for num_nodes keypoints (0 for a negative size or num_nodes >= 2^31). The match rows are read where they
+ * lie, so the size (about 50 bytes per node) does not grow with total_matches. */
+size_t gtsfm_tracks_workspace_bytes(long long num_nodes, long long total_matches);
+
+/* match_idx_dev [total_matches][2] int32, pair p owning rows match_off_dev[p] .. match_off_dev[p+1] (the verifier's layout, see
+ * gtsfm_verify_essential_f64); match_count_dev [num_pairs], inlier_mask_dev [total_matches] and pair_enable_dev [num_pairs] are optional
+ * (NULL: every row / every pair). pair_images_dev [num_pairs][2] = (i1, i2); node_off_dev [num_images + 1], ascending, with
+ * num_nodes = node_off_dev[num_images] < 2^31. kp_xy_dev (optional) [num_nodes][2] float32.
+ * Outputs, capacities in entries with C = min(num_nodes, 2 * total_matches): track_image_dev [C], track_kp_dev [C], track_uv_dev [C][2]
+ * (optional; kp_xy_dev[node] bit for bit), track_off_dev [C + 1] (a track has at least two measurements, so C / 2 + 1 entries are enough
+ * unless a row matches a keypoint to itself, which makes a track of one). Track t owns measurements track_off_dev[t] ..
+ * track_off_dev[t+1]. Tracks are ordered by their smallest (image, keypoint) member, the measurements of a track by image ascending.
+ * counts_dev [8] int32: tracks, measurements, discarded tracks, components (tracks + discarded), rounds, 0, 0, 0.
+ * The labelling runs in rounds of two launches (hook, compress) and the call reads a 4-byte flag from `stream` after each; a round
+ * that hooks nothing ends it, rounds counts that one too. After 64 rounds without a fixed point the call fails with the sizes in
+ * gtsfm_last_error and writes no result. An active row that names an image or a keypoint outside the tables is refused the same way.
+ * num_pairs == 0 or total_matches == 0: zero counts and track_off_dev[0] = 0, nothing else is touched. */
+int gtsfm_tracks_from_matches(const int32_t* match_idx_dev, const long long* match_off_dev, const int32_t* match_count_dev,
+                              const uint8_t* inlier_mask_dev, const uint8_t* pair_enable_dev, const int32_t* pair_images_dev, int num_pairs,
+                              long long total_matches, const long long* node_off_dev, int num_images, const float* kp_xy_dev, void* workspace_dev,
+                              size_t workspace_bytes, long long* track_off_dev, int32_t* track_image_dev, int32_t* track_kp_dev, float* track_uv_dev,
+                              int32_t* counts_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
