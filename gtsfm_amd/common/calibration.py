@@ -22,6 +22,40 @@ class PinholeIntrinsics:
         return np.array([(uv[0] - self.u0) / self.fx, (uv[1] - self.v0) / self.fy])
 
 
+class _Rotation:
+    def __init__(self, matrix: np.ndarray):
+        self._m = np.asarray(matrix, dtype=np.float64).reshape(3, 3)
+
+    def matrix(self) -> np.ndarray:
+        return self._m
+
+
+class _Pose:
+    """The two accessors of ``gtsam.Pose3`` that triangulation reads."""
+
+    def __init__(self, wRc: np.ndarray, wtc: np.ndarray):
+        self._r, self._t = _Rotation(wRc), np.asarray(wtc, dtype=np.float64).reshape(3)
+
+    def rotation(self) -> _Rotation:
+        return self._r
+
+    def translation(self) -> np.ndarray:
+        return self._t
+
+
+class PinholeCamera:
+    """Stand-in for ``gtsam.PinholeCameraCal3Bundler`` where gtsam is absent: ``pose()`` (camera to world) and ``calibration()``."""
+
+    def __init__(self, wRc: np.ndarray, wtc: np.ndarray, intrinsics: PinholeIntrinsics):
+        self._pose, self._cal = _Pose(wRc, wtc), intrinsics
+
+    def pose(self) -> _Pose:
+        return self._pose
+
+    def calibration(self) -> PinholeIntrinsics:
+        return self._cal
+
+
 # calibration classes whose ``calibrate`` is ((u - cx) / fx, (v - cy) / fy) once their distortion coefficients and skew are zero
 # (gtsfm/common/types.py CALIBRATION_TYPE also lists Cal3Fisheye: an equidistant projection even with k1..k4 = 0 -- never pure)
 _PINHOLE_FAMILY = ("PinholeIntrinsics", "Cal3Bundler", "Cal3_S2", "Cal3DS2")

@@ -45,6 +45,26 @@ class VerifiedScene:
         return {"track_off": out["track_off"].cpu().numpy(), "image": out["image"].cpu().numpy(), "kp": out["kp"].cpu().numpy(),
                 "track_uv": out["uv"].cpu().numpy(), "counts": out["counts"]}
 
+    def triangulate(self, cameras: Dict[int, Any], options, edges: Optional[Iterable[Tuple[int, int]]] = None, seed: int = 0) -> Dict[str, Any]:
+        """Tracks -> triangulation (``DataAssociation.run_triangulation``) with the track arrays staying on the device: the CSR arrays
+        that the track builder writes are the triangulation's inputs where they lie. Returns host arrays: ``track_off``, ``image``,
+        ``kp``, ``point`` [T, 3], ``avg_error`` [T], ``exit_code`` [T], ``inlier_mask`` [S]."""
+        from gtsfm_amd.data_association.point3d_initializer import Point3dInitializer
+
+        if self.feats is None:
+            return {"track_off": np.zeros(1, np.int64), "image": np.zeros(0, np.int32), "kp": np.zeros(0, np.int32), "point": np.zeros((0, 3)),
+                    "avg_error": np.zeros(0), "exit_code": np.zeros(0, np.int32), "inlier_mask": np.zeros(0, np.uint8)}
+        if self._engine is None:
+            from gtsfm_amd.runtime.tracks_engine import TracksEngine
+
+            self._engine = TracksEngine(self.feats["xy"].device)
+        xy = self.feats["xy"]
+        trk = self._engine.tracks_from_verified(self.launches, int(xy.shape[1]), int(xy.shape[0]), edges=edges, extra=self.extra, kp_xy=xy.reshape(-1, 2))
+        out = Point3dInitializer(cameras, options, seed=seed, device=xy.device).triangulate_arrays(trk["track_off"], trk["image"], trk["uv"])
+        res = {k: trk[k].cpu().numpy() for k in ("track_off", "image", "kp")}
+        res.update({k: out[k].cpu().numpy() for k in ("point", "avg_error", "exit_code", "inlier_mask")})
+        return res
+
     def tracks_2d(self, edges: Optional[Iterable[Tuple[int, int]]] = None) -> list:
         """The same tracks as ``SfmTrack2d`` objects over ``keypoints_list``'s coordinates."""
         from gtsfm_amd.data_association.dsf_tracks_estimator import tracks_from_csr

@@ -654,6 +654,37 @@ int gtsfm_tracks_from_matches(const int32_t* match_idx_dev, const long long* mat
                               size_t workspace_bytes, long long* track_off_dev, int32_t* track_image_dev, int32_t* track_kp_dev, float* track_uv_dev,
                               int32_t* counts_dev, void* stream);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * Triangulation of feature tracks (float64)
+ *   replaces gtsfm/data_association/point3d_initializer.py:139-295 per track, called from data_assoc.py:205-273.
+ * PARITY UNPINNED towards gtsam: triangulatePoint3(rank_tol = 1e-9, optimize = true) is restated as DLT + 8 damped Gauss-Newton steps
+ * + cheirality, and np.random.choice by a counter-based sampler; the specification is tests/triangulation_reference.py.
+ * mode: 0 NO_RANSAC, 1 RANSAC_SAMPLE_UNIFORM, 2 RANSAC_SAMPLE_BIASED_BASELINE, 3 RANSAC_TOPK_BASELINES. A track of n measurements has
+ * C(n,2) measurement pairs in itertools.combinations order; min(num_hypotheses, C(n,2)) of them are evaluated: all of them, or those
+ * with the smallest sampling keys (splitmix64 of seed, the track's first measurement and the pair index; see the specification).
+ * exit codes: 0 SUCCESS, 1 CHEIRALITY_FAILURE, 2 INLIERS_UNDERCONSTRAINED, 3 POSES_UNDERCONSTRAINED, 4 EXCEEDS_REPROJ_THRESH,
+ * 5 LOW_TRIANGULATION_ANGLE. A track's outputs depend on its own measurements, the cameras and the options only.
+ * ---------------------------------------------------------------------------------------------------------- */
+
+/* Bytes of device workspace (0 for sizes out of range): 8 per track plus 20 per hypothesis record, of which there are at most
+ * min(num_tracks * max_hypotheses, total_measurements * sqrt(max_hypotheses / 2) + num_tracks). max_hypotheses = 0 for NO_RANSAC. */
+size_t gtsfm_triangulate_workspace_bytes(long long num_tracks, long long total_measurements, long long max_hypotheses);
+
+/* The CSR arrays gtsfm_tracks_from_matches writes: track_off_dev [num_tracks + 1] ascending within 0 .. total_measurements,
+ * track_image_dev [total_measurements], track_uv_dev [total_measurements][2] float32 (pixels). cameras_dev [num_images][17] float64:
+ * valid (0: not estimated), fx, fy, cx, cy, wRc row-major, wtc; an image index outside the table counts as not estimated.
+ * reproj_error_threshold > 0, infinity allowed; min_triangulation_angle_deg <= 0 switches the angle test off.
+ * Outputs: point_dev [num_tracks][3] (NaN unless SUCCESS), avg_error_dev [num_tracks] (NaN where the reference returns None),
+ * exit_code_dev [num_tracks], inlier_mask_dev [total_measurements] uint8, stats_dev [num_tracks][4] int32: hypotheses evaluated,
+ * of those skipped (camera missing, underconstrained, cheirality), winning pair index or -1, its votes.
+ * A track with fewer than two measurements gets INLIERS_UNDERCONSTRAINED. The call waits for the stream once, to report offsets that are
+ * not ascending or a track longer than 65535 as GTSFM_ERR_INVALID. */
+int gtsfm_triangulate_tracks_f64(const long long* track_off_dev, const int32_t* track_image_dev, const float* track_uv_dev, long long num_tracks,
+                                 long long total_measurements, const double* cameras_dev, int num_images, int mode, double reproj_error_threshold,
+                                 double min_triangulation_angle_deg, long long num_hypotheses, unsigned long long seed, void* workspace_dev,
+                                 size_t workspace_bytes, double* point_dev, double* avg_error_dev, int32_t* exit_code_dev, uint8_t* inlier_mask_dev,
+                                 int32_t* stats_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
