@@ -164,6 +164,96 @@ def test_determinism(engine, small, mode):
         assert alone["inlier_mask"].tobytes() == first["inlier_mask"][sel].tobytes()
 
 
+# ---- hard geometry against the high-precision arbiter; launch structure at scale ----
+
+from tests.test_triangulation_arbiter_host import FAMILIES, held_to_rule  # noqa: E402
+
+
+@pytest.mark.parametrize("name", list(FAMILIES))
+def test_hard_fixture_against_arbiter(engine, name):
+    """tests/golden/triangulation_hard_scenes.npz (tools/make_triangulation_hard_fixture.py): parallax, world offset, scale, rank, depth,
+    sampler ties and hostile image indices. Discrete outputs equal the arbiter's; cost(x) - cost(minimiser) <= 1e-5 max(1, cost); point
+    and average error within 8 x the port-to-arbiter difference of the family."""
+    fam = FAMILIES[name]
+    held_to_rule(fam, run_device(engine, fam, **fam["options"]), f"device, {name}")
+
+
+def _interleave(small, long_track, copies):
+    """``copies`` x the long track, a short track of the scene after each."""
+    lengths = np.diff(small["track_off"])
+    short = [int(j) for j in np.where((lengths >= 2) & (lengths <= 4))[0]]
+    order = [j for c in range(copies) for j in (long_track, short[c % len(short)])]
+    return _subset(small, order)
+
+
+def test_grid_stride_loop_runs_twice(engine, small):
+    """200 copies of the 75-measurement track at the default 2 749 hypotheses, interleaved with short tracks: 549 800 hypotheses and
+    more, above the 2048 x 256 lanes of the hypothesis kernel's grid. Every copy is byte-equal to the track launched alone (the launch
+    ``test_track_of_75_with_the_default_hypothesis_count`` pins to the restatement)."""
+    j = int(np.argmax(np.diff(small["track_off"])))
+    opts = dict(mode=ref.RANSAC_SAMPLE_UNIFORM, threshold=10.0, num_hypotheses=2749, seed=4)
+    off1, image1, uv1, _ = _subset(small, [j])
+    alone = run_device(engine, small, sub=(off1, image1, uv1), **opts)
+    off, image, uv, _ = _interleave(small, j, 200)
+    out = run_device(engine, small, sub=(off, image, uv), **opts)
+    assert alone["stats"][0, 0] == 2749 and out["stats"][:, 0].sum() > 2048 * 256 and out["stats"][::2, 0].sum() == 549800
+    for k in ("point", "avg_error", "exit_code", "stats"):
+        assert out[k][::2].tobytes() == alone[k].tobytes() * 200, k
+    for c in range(200):
+        assert out["inlier_mask"][off[2 * c] : off[2 * c + 1]].tobytes() == alone["inlier_mask"].tobytes(), c
+
+
+def test_rows_do_not_depend_on_the_batch_size(engine, small):
+    """Prefixes of the scene around the 64 tracks of a final workgroup and the 256 of a count workgroup, and the scene twice over."""
+    off, image, uv = small["track_off"], small["image"], small["uv"]
+    for opts in (dict(mode=ref.NO_RANSAC, threshold=10.0, min_angle_deg=3.0), dict(mode=ref.RANSAC_TOPK_BASELINES, **scenes.LOOSE)):
+        full = run_device(engine, small, **opts)
+        for t in (1, 63, 64, 65, 255, 256, 257):
+            part = run_device(engine, small, sub=(off[: t + 1], image[: off[t]], uv[: off[t]]), **opts)
+            for k in ("point", "avg_error", "exit_code", "stats"):
+                assert part[k].tobytes() == full[k][:t].tobytes(), (t, k)
+            assert part["inlier_mask"].tobytes() == full["inlier_mask"][: off[t]].tobytes(), t
+        twice = run_device(engine, small, sub=(np.concatenate([off, off[1:] + off[-1]]), np.tile(image, 2), np.tile(uv, (2, 1))), **opts)
+        assert len(twice["exit_code"]) == 602
+        for k in OUTPUTS:
+            assert twice[k].tobytes() == full[k].tobytes() * 2, k
+
+
+def test_a_call_does_not_depend_on_what_the_workspace_held(gpu_device, small):
+    """The cached workspace, sized by a larger call, is filled with 0xFF before a smaller one: the bytes equal a fresh engine's."""
+    from gtsfm_amd.runtime.triangulation_engine import TriangulationEngine
+
+    lengths = np.diff(small["track_off"])
+    sub = _subset(small, [int(j) for j in np.where(lengths >= 3)[0][:70]])[:3]
+    for opts in (dict(mode=ref.NO_RANSAC, threshold=10.0), dict(mode=ref.RANSAC_SAMPLE_UNIFORM, **scenes.LOOSE), dict(mode=ref.RANSAC_TOPK_BASELINES, **scenes.LOOSE)):
+        fresh = run_device(TriangulationEngine(gpu_device), small, sub=sub, **opts)
+        used = TriangulationEngine(gpu_device)
+        run_device(used, small, **dict(opts, num_hypotheses=2749))
+        size = used._ws.numel()
+        used._ws.fill_(0xFF)
+        again = run_device(used, small, sub=sub, **opts)
+        assert used._ws.numel() == size  # the same allocation served the smaller call
+        assert all(again[k].tobytes() == fresh[k].tobytes() for k in OUTPUTS), opts
+
+
+def test_longest_track_is_accepted_and_one_more_is_refused(engine, small):
+    table = small["cameras"]
+    valid = [i for i in range(scenes.NUM_CAMERAS) if i not in scenes.INVALID]
+    x = np.array([0.4, -0.7, 0.2])
+    pixel = {i: ref.project(table[i], x)[:2] for i in valid}
+    for n in (65535, 65536):
+        image = np.array([valid[k % len(valid)] for k in range(n)], np.int32)
+        uv = np.array([pixel[i] for i in image], np.float32)
+        off = np.array([0, n], np.int64)
+        if n == 65535:
+            out = run_device(engine, small, sub=(off, image, uv), mode=ref.NO_RANSAC)
+            assert out["exit_code"][0] == ref.SUCCESS and out["inlier_mask"].all() and out["avg_error"][0] < 1e-3
+            np.testing.assert_allclose(out["point"][0], x, rtol=0, atol=1e-5)  # float32 pixels
+        else:
+            with pytest.raises(RuntimeError, match="longer than"):
+                run_device(engine, small, sub=(off, image, uv), mode=ref.NO_RANSAC)
+
+
 def _circle_cameras():
     from gtsfm_amd.common.calibration import PinholeCamera, PinholeIntrinsics
     from tests.test_triangulation_host import circle_scene

@@ -26,6 +26,20 @@ draws the same pairs wherever it stands in a batch. When ``num_hypotheses`` equa
 reference's permutation only reorders them; exact ties go to the lowest pair index, one of the reference's own possible outcomes.
 
 Sums over a track's measurements run in measurement order.
+
+Validity domain
+---------------
+``dlt`` (numpy's SVD) resolves a singular value to about eps x sigma_max ABSOLUTE, so on badly scaled scenes it is less accurate than
+the device, whose Givens / one-sided Jacobi keeps small singular values to relative accuracy. ``dlt_jacobi`` is a float64 port of the
+device's solve; ``triangulate_point(..., solver="jacobi")`` uses it. The default stays numpy: the Lund door fixture was recorded with
+it. Measured against the high-precision arbiter (tests/triangulation_arbiter.py; figures in profiles/triangulation_hard_scenes.txt):
+with the numpy solver the restatement agrees with the arbiter on the synthetic scenes and the Lund door (point 1.1e-8 relative, average
+error 4.6e-7 px at worst, inside the tolerances those scenes use) and is a valid specification within about 1e3 units of the origin. On
+the 8-camera circle at world offset (5e5, 4e6, 100) its DLT point for a neighbour pair is 3.3e-3 units off (6.4e-10 with the port) and
+it reports rank 3 for a facing pair whose exact sigma_3 is 4e-15; near rank deficiency (sigma_3 <= 1e-6) its points are up to 0.55
+relative off where the port's are 8e-9. With EITHER solver the fixed ``GN_STEPS`` hold the cost within 1e-5 max(1, cost) of the minimum
+down to baseline / depth 1e-5 near the origin, but not at baseline / depth 1e-3 with a world offset of 1e5 or more: the homogeneous DLT
+is not invariant under translation and starts too far away (gap 9.5e-5, or another winning pair). No test compares the device there.
 """
 
 from __future__ import annotations
@@ -37,6 +51,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import numpy as np
 
 GN_STEPS = 8
+JACOBI_SWEEPS = 10
 RANK_TOL = 1e-9
 LAMBDA_INITIAL, LAMBDA_FACTOR, LAMBDA_FLOOR = 1e-5, 10.0, 1e-20
 MAX_TRACK_REPROJ_ERROR = float(np.finfo(np.float32).max)
@@ -142,6 +157,75 @@ def dlt(cams: Sequence[np.ndarray], uvs: Sequence[np.ndarray]) -> Optional[np.nd
     return v[:3] / v[3]
 
 
+def givens_row(r: List[List[float]], a: List[float]) -> None:
+    """Rotates one row into the 4 x 4 upper triangle ``r`` (the device's ``tri_givens_row``)."""
+    for j in range(4):
+        h = math.sqrt(r[j][j] * r[j][j] + a[j] * a[j])
+        if a[j] == 0.0 or not h > 0.0:
+            continue
+        c, s = r[j][j] / h, a[j] / h
+        for k in range(j, 4):
+            t = c * r[j][k] + s * a[k]
+            a[k] = c * a[k] - s * r[j][k]
+            r[j][k] = t
+
+
+def jacobi_triangle(g: List[List[float]], sweeps: int = JACOBI_SWEEPS) -> Tuple[List[float], List[List[float]]]:
+    """One-sided Jacobi (Hestenes) on the columns of ``g`` (destroyed): the column norms and V (the device's ``tri_dlt_solve``)."""
+    v = [[1.0 if i == j else 0.0 for j in range(4)] for i in range(4)]
+    for _ in range(sweeps):
+        for p in range(3):
+            for q in range(p + 1, 4):
+                alpha = beta = gamma = 0.0
+                for i in range(4):
+                    alpha += g[i][p] * g[i][p]
+                    beta += g[i][q] * g[i][q]
+                    gamma += g[i][p] * g[i][q]
+                if not abs(gamma) > 1.0e-17 * math.sqrt(alpha * beta):
+                    continue
+                zeta = (beta - alpha) / (2.0 * gamma)
+                t = (1.0 if zeta >= 0.0 else -1.0) / (abs(zeta) + math.sqrt(1.0 + zeta * zeta))
+                c = 1.0 / math.sqrt(1.0 + t * t)
+                s = c * t
+                for i in range(4):
+                    gp, gq = g[i][p], g[i][q]
+                    g[i][p], g[i][q] = c * gp - s * gq, s * gp + c * gq
+                    vp, vq = v[i][p], v[i][q]
+                    v[i][p], v[i][q] = c * vp - s * vq, s * vp + c * vq
+    sigma = [math.sqrt(g[0][j] * g[0][j] + g[1][j] * g[1][j] + g[2][j] * g[2][j] + g[3][j] * g[3][j]) for j in range(4)]
+    return sigma, v
+
+
+def dlt_jacobi(cams: Sequence[np.ndarray], uvs: Sequence[np.ndarray]) -> Optional[np.ndarray]:
+    """Float64 port of the device's DLT: Givens row insertion in measurement order, ``JACOBI_SWEEPS`` Hestenes sweeps with the 1e-17
+    skip test, rank against ``RANK_TOL``, the column of the smallest norm (the first one among equals)."""
+    r = [[0.0] * 4 for _ in range(4)]
+    with np.errstate(all="ignore"):
+        for cam, uv in zip(cams, uvs):
+            cam = [float(c) for c in cam]
+            rot, t = cam[5:14], cam[14:17]
+            p = [[rot[j], rot[3 + j], rot[6 + j], -(rot[j] * t[0] + rot[3 + j] * t[1] + rot[6 + j] * t[2])] for j in range(3)]
+            u, w = float(uv[0]), float(uv[1])
+            a = [u * p[2][k] - (cam[1] * p[0][k] + cam[3] * p[2][k]) for k in range(4)]
+            b = [w * p[2][k] - (cam[2] * p[1][k] + cam[4] * p[2][k]) for k in range(4)]
+            givens_row(r, a)
+            givens_row(r, b)
+        try:
+            sigma, v = jacobi_triangle(r)
+        except (OverflowError, ValueError):
+            return None
+        if sum(1 for s in sigma if s > RANK_TOL) < 3:
+            return None
+        last, smallest = 0, math.inf
+        for j in range(4):
+            if sigma[j] < smallest:
+                smallest, last = sigma[j], j
+        return np.array([v[0][last], v[1][last], v[2][last]]) / np.float64(v[3][last])
+
+
+SOLVERS = {"numpy": dlt, "jacobi": dlt_jacobi}
+
+
 def _normal_equations(cams, uvs, x):
     """cost = 1/2 sum r^2, H = J^T J (upper triangle as 6 numbers), g = J^T r; sums in measurement order."""
     cost, h, g = 0.0, [0.0] * 6, [0.0] * 3
@@ -211,10 +295,11 @@ def refine(cams, uvs, x: np.ndarray, steps: int = GN_STEPS) -> Optional[np.ndarr
     return x
 
 
-def triangulate_point(cams, uvs, steps: int = GN_STEPS) -> Optional[np.ndarray]:
-    """gtsam.triangulatePoint3(..., rank_tol=1e-9, optimize=True); None where it raises."""
+def triangulate_point(cams, uvs, steps: int = GN_STEPS, solver: str = "numpy") -> Optional[np.ndarray]:
+    """gtsam.triangulatePoint3(..., rank_tol=1e-9, optimize=True); None where it raises. ``solver``: "numpy" (LAPACK's SVD) or
+    "jacobi" (the float64 port of the device's solve, see the validity domain above)."""
     with np.errstate(all="ignore"):
-        x = dlt(cams, uvs)
+        x = SOLVERS[solver](cams, uvs)
         if x is None or not np.all(np.isfinite(x)):
             return None
         x = refine(cams, uvs, x, steps)
@@ -253,7 +338,8 @@ def max_triangulation_angle_deg(table: np.ndarray, x: np.ndarray, images: Sequen
 
 
 def triangulate_track(table: np.ndarray, images: Sequence[int], uv: np.ndarray, mode: int = NO_RANSAC, threshold: float = math.inf,
-                      min_angle_deg: float = 0.0, num_hypotheses: int = 2749, seed: int = 0, steps: int = GN_STEPS, detail: Optional[dict] = None):
+                      min_angle_deg: float = 0.0, num_hypotheses: int = 2749, seed: int = 0, steps: int = GN_STEPS, detail: Optional[dict] = None,
+                      solver: str = "numpy"):
     """One track: (point [3] or NaNs, average error or NaN, exit code, inlier mask [n], stats [4]). ``uv`` float64 (n, 2); ``detail``
     receives the per-hypothesis (votes, mean error, inlier mask) of a RANSAC run, for the fixture's decisiveness test."""
     images = [int(i) for i in images]
@@ -272,7 +358,7 @@ def triangulate_track(table: np.ndarray, images: Sequence[int], uv: np.ndarray, 
         for p in chosen:
             k1, k2 = pairs[p]
             c1, c2 = _camera(table, images[k1]), _camera(table, images[k2])
-            x = None if c1 is None or c2 is None else triangulate_point([c1, c2], [uv[k1], uv[k2]], steps)
+            x = None if c1 is None or c2 is None else triangulate_point([c1, c2], [uv[k1], uv[k2]], steps, solver)
             if x is None:
                 stats[1] += 1
                 continue
@@ -296,7 +382,7 @@ def triangulate_track(table: np.ndarray, images: Sequence[int], uv: np.ndarray, 
     used = [k for k in idx if _camera(table, images[k]) is not None]
     if len(used) < 2:
         return nan3, math.nan, POSES_UNDERCONSTRAINED, inl, stats
-    x = triangulate_point([table[images[k]] for k in used], [uv[k] for k in used], steps)
+    x = triangulate_point([table[images[k]] for k in used], [uv[k] for k in used], steps, solver)
     if x is None:
         return nan3, math.nan, CHEIRALITY_FAILURE, inl, stats
     err = reprojection_errors(table, x, [images[k] for k in idx], uv[idx])

@@ -1,0 +1,177 @@
+// Stand-alone host build of the triangulation kernels' per-track arithmetic (the TRI_HD functions of
+// gtsfm_amd/csrc/triangulation_kernels.hip), for running it on a CPU and under the host sanitizers:
+//
+//   hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off [-Xarch_host -fsanitize=address,undefined] -c tools/triangulation_host_main.cpp -o main.o
+//   hipcc [-fsanitize=address,undefined] main.o -o triangulation_host
+//   triangulation_host scene.bin out.bin
+//
+// scene.bin: int64 {magic, T, S, num_images, mode, num_hypotheses, seed, 0}, double {threshold, min_angle_deg}, int64 track_off[T + 1],
+// int32 image[S], float uv[2 S], double cameras[17 num_images]. out.bin: two copies (one per lane partition, see below) of double
+// point[3 T], double avg_error[T], int32 exit_code[T], uint8 inlier_mask[S], int32 stats[4 T].
+//
+// The stages are the device call's: count -> serial scan -> select -> hypothesis -> final. They run twice: with one lane doing all the
+// work (first 0, stride 1) over a zeroed workspace, and with the device's partition (select: 256 lanes per track; hypothesis: a grid
+// of min(ceil(cap / 256), 2048) x 256 lanes, grid-stride) over a workspace filled with 0xFF. The two outputs must be byte-equal: exit
+// status 2 when they are not, 3 / 4 for the two error flags of the device call (nothing written), 1 for a bad file. Every input array
+// is a heap allocation of its exact size, so a read outside it is a sanitizer report.
+
+#include <stdarg.h>
+#include <stdlib.h>
+#include <string.h>
+
+#include <vector>
+
+#include "../gtsfm_amd/csrc/triangulation_kernels.hip"
+
+void gtsfm_set_error(const char* fmt, ...) {
+    va_list args;
+    va_start(args, fmt);
+    vfprintf(stderr, fmt, args);
+    va_end(args);
+    fputc('\n', stderr);
+}
+
+namespace {
+
+const long long SCENE_MAGIC = 0x3149525453464754ll;  // "TGFSTRI1"
+
+struct Scene {
+    long long num_tracks, total, num_images, mode, num_hyp;
+    unsigned long long seed;
+    double threshold, min_angle;
+    long long* track_off;
+    int* image;
+    float* uv;
+    double* cams;
+};
+
+template <class T>
+T* read_array(FILE* f, size_t n) {
+    T* p = (T*)malloc(n ? n * sizeof(T) : 1);  // exact size: the sanitizer sees every read past the end
+    if (p && n && fread(p, sizeof(T), n, f) != n) {
+        free(p);
+        return nullptr;
+    }
+    return p;
+}
+
+bool read_scene(const char* path, Scene& s) {
+    FILE* f = fopen(path, "rb");
+    if (!f) return false;
+    long long head[8];
+    double opts[2];
+    bool ok = fread(head, 8, 8, f) == 8 && fread(opts, 8, 2, f) == 2 && head[0] == SCENE_MAGIC && head[1] >= 0 && head[2] >= 0 && head[3] >= 0 &&
+              head[1] < (1ll << 31) && head[2] < (1ll << 31) && head[3] < (1ll << 31);
+    if (ok) {
+        s.num_tracks = head[1];
+        s.total = head[2];
+        s.num_images = head[3];
+        s.mode = head[4];
+        s.num_hyp = head[5];
+        s.seed = (unsigned long long)head[6];
+        s.threshold = opts[0];
+        s.min_angle = opts[1];
+        s.track_off = read_array<long long>(f, (size_t)s.num_tracks + 1);
+        s.image = read_array<int>(f, (size_t)s.total);
+        s.uv = read_array<float>(f, 2 * (size_t)s.total);
+        s.cams = read_array<double>(f, 17 * (size_t)s.num_images);
+        ok = s.track_off && s.image && s.uv && s.cams;
+    }
+    fclose(f);
+    return ok;
+}
+
+struct Outputs {
+    std::vector<double> point, avg;
+    std::vector<int> code, stats;
+    std::vector<uint8_t> mask;
+    Outputs(const Scene& s) : point(3 * s.num_tracks, NAN), avg(s.num_tracks, NAN), code(s.num_tracks, 0), stats(4 * s.num_tracks, 0), mask(s.total, 0) {}
+    bool same(const Outputs& o) const {
+        auto eq = [](const void* a, const void* b, size_t n) { return n == 0 || memcmp(a, b, n) == 0; };
+        return eq(point.data(), o.point.data(), point.size() * 8) && eq(avg.data(), o.avg.data(), avg.size() * 8) &&
+               eq(code.data(), o.code.data(), code.size() * 4) && eq(stats.data(), o.stats.data(), stats.size() * 4) &&
+               eq(mask.data(), o.mask.data(), mask.size());
+    }
+    bool write(FILE* f) const {
+        auto put = [&](const void* p, size_t n) { return n == 0 || fwrite(p, 1, n, f) == n; };
+        return put(point.data(), point.size() * 8) && put(avg.data(), avg.size() * 8) && put(code.data(), code.size() * 4) && put(mask.data(), mask.size()) &&
+               put(stats.data(), stats.size() * 4);
+    }
+};
+
+// 0, or the error flag's exit status
+int run(const Scene& s, bool device_partition, Outputs& out) {
+    const int mode = (int)s.mode;
+    const long long max_hyp = mode == TRI_NO_RANSAC ? 0 : s.num_hyp;
+    const size_t bytes = tri_layout(nullptr, s.num_tracks, s.total, max_hyp).bytes;
+    void* base = aligned_alloc(256, bytes);
+    if (!base) return 1;
+    memset(base, device_partition ? 0xFF : 0x00, bytes);
+    const TriWorkspace w = tri_layout(base, s.num_tracks, s.total, max_hyp);
+    memset(w.flags, 0, 16);
+    for (long long t = 0; t < s.num_tracks; ++t) tri_count_track(t, s.track_off, s.num_tracks, s.total, mode, max_hyp, w.hyp_off, w.flags);
+    long long carry = 0;
+    for (long long t = 0; t < s.num_tracks; ++t) {  // the scan kernel, serially
+        const long long x = w.hyp_off[t];
+        w.hyp_off[t] = carry;
+        carry += x;
+    }
+    w.hyp_off[s.num_tracks] = carry;
+    if (carry > w.cap) w.flags[1] = 1;
+    if (mode != TRI_NO_RANSAC) {
+        const int select_lanes = device_partition ? TRI_THREADS : 1;
+        for (long long t = 0; t < s.num_tracks; ++t)
+            for (int lane = 0; lane < select_lanes; ++lane)
+                tri_select_track(t, lane, select_lanes, s.track_off, s.image, s.uv, s.cams, (int)s.num_images, mode, max_hyp, s.seed, w.hyp_off, w.sel, w.cap, w.flags);
+        const long long want = (w.cap + TRI_THREADS - 1) / TRI_THREADS;
+        const long long lanes = device_partition ? (want < TRI_HYP_BLOCKS ? want : TRI_HYP_BLOCKS) * TRI_THREADS : 1;
+        for (long long lane = 0; lane < lanes; ++lane)
+            tri_hypothesis_lane(lane, lanes, s.track_off, s.image, s.uv, s.num_tracks, s.cams, (int)s.num_images, s.threshold, max_hyp, w.hyp_off, w.sel, w.hyp, w.cap,
+                                w.flags);
+    }
+    for (long long t = 0; t < s.num_tracks; ++t)
+        tri_final_track(t, s.track_off, s.image, s.uv, s.num_tracks, s.cams, (int)s.num_images, mode, s.threshold, s.min_angle, w.hyp_off, w.hyp, w.cap, w.flags,
+                        out.point.data(), out.avg.data(), out.code.data(), out.mask.data(), out.stats.data());
+    const int status = w.flags[0] ? 3 : (w.flags[1] ? 4 : 0);
+    free(base);
+    return status;
+}
+
+}  // namespace
+
+int main(int argc, char** argv) {
+    if (argc != 3) {
+        fprintf(stderr, "usage: %s scene.bin out.bin\n", argv[0]);
+        return 1;
+    }
+    Scene s;
+    if (!read_scene(argv[1], s)) {
+        fprintf(stderr, "%s: not a scene file\n", argv[1]);
+        return 1;
+    }
+    if (s.mode < TRI_NO_RANSAC || s.mode > TRI_TOPK || !(s.threshold > 0.0) || (s.mode != TRI_NO_RANSAC && s.num_hyp < 0)) {
+        fprintf(stderr, "%s: options outside the device call's domain\n", argv[1]);
+        return 1;
+    }
+    Outputs serial(s), device(s);
+    int status = 0;
+    if (s.num_tracks > 0) {
+        status = run(s, false, serial);
+        const int second = run(s, true, device);
+        if (status != second) status = 2;
+    }
+    if (status == 0 && !serial.same(device)) {
+        fprintf(stderr, "the outputs depend on the lane partition or on what the workspace held\n");
+        status = 2;
+    }
+    if (status == 0) {
+        FILE* f = fopen(argv[2], "wb");
+        if (!f || !serial.write(f) || !device.write(f)) status = 1;
+        if (f) fclose(f);
+    }
+    free(s.track_off);
+    free(s.image);
+    free(s.uv);
+    free(s.cams);
+    return status;
+}
