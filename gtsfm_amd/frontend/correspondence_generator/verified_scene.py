@@ -24,10 +24,128 @@ class VerifiedScene:
         self.feats = feats
         self.launches = launches
         self.extra = extra
+        self.two_view_stats: Dict[Tuple[int, int], Dict[str, Any]] = {}  # filled by two_view()
         self._engine = None
 
     def as_tuple(self):
         return self.keypoints_list, self.putative, self.verified
+
+    def two_view(self, options=None, camera_intrinsics: Optional[List[Any]] = None) -> "VerifiedScene":
+        """The rest of ``TwoViewEstimator.run_2view`` for every edge that was verified on the device (``two_view_estimator.py:411-450``):
+        two-view bundle adjustment (``gtsfm_two_view_ba_f64``, one call per verifier launch, on the launch's arrays where they lie) and
+        the ``InlierSupportProcessor``'s two tests (``inlier_support_processor.py:73-95``: the inlier ratio first, then the inlier
+        count of a model that has inliers). Returns a NEW scene; this one is untouched. Its launches carry the refined poses and the
+        valid mask in place of the inlier mask (zeroed for edges without support), so ``tracks()`` / ``triangulate()`` on it see what
+        the reference's multi-view stage sees, and no correspondence is downloaded for them. ``verified`` holds the post-ISP tuples
+        (built from one download per launch) and ``two_view_stats`` the per-edge status, counts and step counts. The reference's hack
+        ``post_ba_inlier_ratio = pre_ba_inlier_ratio`` (``:423-426``) is kept. ``options``: ``gtsfm_amd.bundle.two_view_ba.TwoViewOptions``;
+        ``camera_intrinsics``: a calibration per image (a non-pinhole one raises ``NotImplementedError``).
+        Edges in ``extra`` (verified through the per-pair host fallback) go through the per-pair drop-in: ``TwoViewEstimator.bundle_adjust``
+        on their verified tuple and keypoints (when they have at least ``min_num_inliers_est_model`` correspondences, ``:412``), then
+        ``InlierSupportProcessor.run_inlier_support``; the new scene's ``extra`` holds their post-ISP correspondences. A calibration that
+        is not a pure pinhole raises ``NotImplementedError`` naming it there as well."""
+        from gtsfm_amd.bundle.two_view_ba import TwoViewOptions
+        from gtsfm_amd.frontend.verifier.ransac import _to_pose_types
+        from gtsfm_amd.runtime.pipeline import FrontEndPipeline
+        from gtsfm_amd.runtime.two_view_ba_engine import STATUS_NAMES
+
+        opt = options or TwoViewOptions()
+        failure = (None, None, np.array([], dtype=np.uint64), 0.0)
+        verified = dict(self.verified)
+        stats_by_edge: Dict[Tuple[int, int], Dict[str, Any]] = {}
+        launches: List[Dict[str, Any]] = []
+        poses: Dict[Tuple[int, int], Tuple[np.ndarray, np.ndarray]] = {}
+        if self.feats is not None and self.launches:
+            import torch
+
+            xy = self.feats["xy"]
+            cap, table = int(xy.shape[1]), xy.reshape(-1, 2)
+            ba = opt.optimizer() if opt.bundle_adjust_2view else None
+            if ba is not None and camera_intrinsics is None:
+                raise ValueError("two_view needs camera_intrinsics for the bundle adjustment")
+            for ver in self.launches:
+                pairs = [tuple(p) for p in ver["pairs"]]
+                pre = ver["stats"][:, 0].cpu().numpy().astype(np.int64)  # the verifier's inlier counts
+                if ba is None:
+                    rot, trans, mask, valid = ver["R"], ver["t"], ver["mask"], pre
+                    ba_stats = np.zeros((len(pairs), 8), np.int32)
+                    ba_stats[:, 0], ba_stats[:, 1], ba_stats[:, 3] = 1, pre, pre  # SKIPPED: the verifier's result passes through
+                else:
+                    out = ba.run_launch(
+                        {"kp_xy": table, "kp_off1": [i * cap for i, _ in pairs], "kp_off2": [j * cap for _, j in pairs], "match_idx": ver["match_idx"],
+                         "match_off": list(ver["match_off"]), "match_count": ver["match_count"], "inlier_mask": ver["mask"],
+                         "intrinsics": [ba.pair_intrinsics(camera_intrinsics[i], camera_intrinsics[j]) for i, j in pairs], "rotation": ver["R"], "translation": ver["t"]},
+                        device=xy.device, min_verified=opt.min_num_inliers_est_model, triangulation_threshold=opt.triangulation_reproj_error_threshold,
+                        triangulation_min_angle_deg=opt.triangulation_min_angle_deg)
+                    rot, trans, mask, ba_stats = out["rotation"], out["translation"], out["valid_mask"], out["stats"]
+                    valid = ba_stats[:, 3].astype(np.int64)
+                # InlierSupportProcessor: the ratio is the verifier's (the reference's hack), the count is the post-adjustment one
+                ratio = np.array([verified[p][3] if p in verified and verified[p][0] is not None else 0.0 for p in pairs], dtype=np.float64)
+                supported = ~(ratio < opt.min_inlier_ratio_est_model) & ~((valid > 0) & (valid < opt.min_num_inliers_est_model))
+                lengths = torch.from_numpy(np.diff(np.asarray(list(ver["match_off"]), dtype=np.int64))).to(xy.device)
+                rows = torch.repeat_interleave(torch.from_numpy(supported.astype(np.uint8)).to(xy.device), lengths)
+                stats = ver["stats"].clone()
+                stats[:, 0] = torch.from_numpy(np.where(supported, valid, 0).astype(np.int32)).to(xy.device)
+                new = dict(ver)
+                new.update(R=rot, t=trans, mask=(mask * rows).contiguous(), stats=stats, two_view=ba_stats)
+                launches.append(new)
+                rot_host, trans_host = rot.cpu().numpy().reshape(-1, 3, 3), trans.cpu().numpy().reshape(-1, 3)
+                for k, p in enumerate(pairs):
+                    poses[p] = (rot_host[k], trans_host[k])
+                    stats_by_edge[p] = {"status": STATUS_NAMES[int(ba_stats[k, 0])], "verified": int(ba_stats[k, 1]), "triangulated": int(ba_stats[k, 2]),
+                                        "valid": int(ba_stats[k, 3]), "accepted_steps": int(ba_stats[k, 4]), "solves_tried": int(ba_stats[k, 5]),
+                                        "supported": bool(supported[k])}
+            for pair, res in FrontEndPipeline.verified_to_numpy(launches).items():
+                if pair not in self.verified or pair in self.extra:
+                    continue
+                old = self.verified[pair]
+                rot_np, dir_np = poses[pair]
+                corr = res["v_corr_idxs"].astype(np.asarray(old[2]).dtype if np.asarray(old[2]).ndim == 2 else np.int32).reshape(-1, 2)
+                posed = bool(np.isfinite(rot_np).all() and np.isfinite(dir_np).all())
+                if stats_by_edge[pair]["status"] == "NONE_TRIANGULATED" or (stats_by_edge[pair]["status"] == "INDETERMINATE" and not posed):
+                    corr = np.zeros(shape=(0, 2), dtype=np.int32)  # bundle_adjust's own early returns (two_view_estimator.py:263, 276)
+                if not stats_by_edge[pair]["supported"]:
+                    verified[pair] = failure
+                elif posed:
+                    verified[pair] = (*_to_pose_types(rot_np, dir_np), corr, old[3])
+                else:
+                    verified[pair] = (None, None, corr, old[3])
+        extra: Dict[Tuple[int, int], np.ndarray] = {}
+        if self.extra:
+            from gtsfm_amd.data_association.point3d_initializer import TriangulationOptions, TriangulationSamplingMode
+            from gtsfm_amd.frontend.inlier_support_processor import InlierSupportProcessor
+            from gtsfm_amd.two_view_estimator import TwoViewEstimator, generate_two_view_report
+
+            isp = InlierSupportProcessor(opt.min_num_inliers_est_model, opt.min_inlier_ratio_est_model)
+            estimator = TwoViewEstimator(None, isp, opt.bundle_adjust_2view, 4.0,
+                                         TriangulationOptions(mode=TriangulationSamplingMode.NO_RANSAC, reproj_error_threshold=opt.triangulation_reproj_error_threshold,
+                                                              min_triangulation_angle=opt.triangulation_min_angle_deg),
+                                         bundle_adjust_2view_maxiters=opt.bundle_adjust_2view_maxiters, ba_reproj_error_thresholds=opt.ba_reproj_error_thresholds,
+                                         allow_indeterminate_linear_system=opt.allow_indeterminate_linear_system)
+            if opt.bundle_adjust_2view and camera_intrinsics is None:
+                raise ValueError("two_view needs camera_intrinsics for the bundle adjustment")
+            for pair in self.extra:
+                i1, i2 = pair
+                rot_obj, dir_obj, corr, ratio = self.verified[pair]
+                row = None
+                if opt.bundle_adjust_2view and len(corr) >= opt.min_num_inliers_est_model:  # two_view_estimator.py:412
+                    rot_obj, dir_obj, corr, row = estimator.bundle_adjust_with_stats(self.keypoints_list[i1], self.keypoints_list[i2], corr, camera_intrinsics[i1],
+                                                                                     camera_intrinsics[i2], rot_obj, dir_obj, None)
+                report = generate_two_view_report(ratio, np.asarray(corr).reshape(-1, 2) if np.asarray(corr).size else np.zeros((0, 2), np.int32))
+                isp_rot, isp_dir, isp_corr, _ = isp.run_inlier_support(rot_obj, dir_obj, corr, report)
+                count = int(np.asarray(corr).reshape(-1, 2).shape[0])
+                supported = not (ratio < opt.min_inlier_ratio_est_model) and not (0 < count < opt.min_num_inliers_est_model)  # what the processor decided
+                verified[pair] = (isp_rot, isp_dir, isp_corr, ratio) if supported else failure
+                extra[pair] = isp_corr
+                info = {"status": "SKIPPED" if row is None and (not opt.bundle_adjust_2view or len(self.verified[pair][2]) < opt.min_num_inliers_est_model)
+                        else ("NO_INITIAL_POSE" if row is None else STATUS_NAMES[int(row[0])]), "verified": int(len(self.verified[pair][2])),
+                        "valid": count, "supported": bool(supported), "host_fallback": True}
+                if row is not None:
+                    info.update(triangulated=int(row[2]), accepted_steps=int(row[4]), solves_tried=int(row[5]))
+                stats_by_edge[pair] = info
+        scene = VerifiedScene(self.keypoints_list, self.putative, verified, self.feats, launches if launches else list(self.launches), extra)
+        scene.two_view_stats = stats_by_edge
+        return scene
 
     def tracks(self, edges: Optional[Iterable[Tuple[int, int]]] = None) -> Dict[str, Any]:
         """The feature tracks of the verified correspondences (of ``edges`` only, when given: ``filter_corr_by_idx`` followed by

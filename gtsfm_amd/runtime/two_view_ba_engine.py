@@ -1,0 +1,105 @@
+"""Host side of the device two-view bundle adjustment: ``gtsfm_two_view_ba_f64`` refines every pair of one verifier launch in one call,
+replacing the per-pair ``TwoViewEstimator.bundle_adjust`` of ``gtsfm/two_view_estimator.py:212-288`` (triangulation, gtsam factor graph,
+Levenberg-Marquardt, reprojection filter). PyTorch provides device memory and copies only; only the per-pair stats are read back.
+PARITY UNPINNED towards gtsam (see ``tests/two_view_ba_reference.py``)."""
+
+from __future__ import annotations
+
+import dataclasses
+import math
+from typing import Dict, Optional
+
+import numpy as np
+
+STATUS_NAMES = ("OK", "SKIPPED", "NO_INITIAL_POSE", "NONE_TRIANGULATED", "INDETERMINATE")
+STATS_FIELDS = ("status", "verified", "triangulated", "valid", "accepted_steps", "solves_tried", "spare0", "spare1")
+
+
+@dataclasses.dataclass(frozen=True)
+class TwoViewBAOptions:
+    """The values ``TwoViewEstimator.__init__`` configures (``unified.yaml``), and gtsam's noise models of ``bundle_adjustment.py``."""
+
+    max_iterations: int = 100
+    reproj_error_threshold: float = 0.5
+    huber_k: float = 1.345  # math.inf: RobustBAMode.NONE
+    measurement_sigma: float = 1.0
+    pose_prior_sigma: float = 0.1
+    point_prior_sigma: float = 0.1
+    min_verified: int = 15  # InlierSupportProcessor.min_num_inliers_est_model
+    allow_indeterminate: bool = False
+    triangulation_threshold: float = math.inf
+    triangulation_min_angle_deg: float = 0.0
+
+
+class TwoViewBAEngine:
+    """Lib handle and a cached workspace; one instance per process / GPU."""
+
+    def __init__(self, device=None):
+        import torch
+
+        from gtsfm_amd.runtime import lib as _lib
+        from gtsfm_amd.runtime.superpoint_engine import require_gpu
+
+        self._torch = torch
+        self.device = require_gpu(device)
+        self._L = _lib
+        self._lib = _lib.load()
+        self._ws = None
+
+    def _workspace(self, num_pairs: int, total: int):
+        need = int(self._lib.gtsfm_two_view_ba_workspace_bytes(num_pairs, total))
+        if need == 0:
+            raise ValueError(f"gtsfm_two_view_ba_workspace_bytes refuses {num_pairs} pairs / {total} matches")
+        if self._ws is None or self._ws.numel() < need:
+            self._ws = self._torch.empty(need + 256, dtype=self._torch.uint8, device=self.device)
+        return self._ws
+
+    def _dev(self, a, dtype, np_dtype):
+        torch = self._torch
+        if isinstance(a, torch.Tensor):
+            return a.to(device=self.device, dtype=dtype).contiguous()
+        return torch.from_numpy(np.ascontiguousarray(a, dtype=np_dtype)).to(self.device)
+
+    def run(self, launch: Dict[str, object], options: Optional[TwoViewBAOptions] = None) -> Dict[str, object]:
+        """``launch``: one verifier launch's arrays, device tensors (used where they lie) or host arrays -- ``kp_xy`` [*, 2] float32,
+        ``kp_off1`` / ``kp_off2`` [P] int64, ``match_idx`` [M, 2] int32, ``match_off`` [P + 1] int64, ``match_count`` [P] int32 or None,
+        ``inlier_mask`` [M] uint8, ``intrinsics`` [P, 8] float64, ``rotation`` [P, 3, 3] / ``translation`` [P, 3] float64.
+        Returns device tensors ``rotation`` [P, 3, 3], ``translation`` [P, 3], ``valid_mask`` [M] uint8, ``point`` [M, 3], ``cost`` [P, 2],
+        and ``stats`` [P, 8] int32 on the host (``STATS_FIELDS``): the only readback. ``match_off`` is checked on the device (not ascending within
+        0 .. M raises)."""
+        torch = self._torch
+        opt = options or TwoViewBAOptions()
+        kp = self._dev(launch["kp_xy"], torch.float32, np.float32).reshape(-1, 2)
+        off1 = self._dev(launch["kp_off1"], torch.int64, np.int64)
+        off2 = self._dev(launch["kp_off2"], torch.int64, np.int64)
+        idx = self._dev(launch["match_idx"], torch.int32, np.int32).reshape(-1, 2)
+        moff = self._dev(launch["match_off"], torch.int64, np.int64)
+        count = None if launch.get("match_count") is None else self._dev(launch["match_count"], torch.int32, np.int32)
+        mask = self._dev(launch["inlier_mask"], torch.uint8, np.uint8)
+        intr = self._dev(launch["intrinsics"], torch.float64, np.float64).reshape(-1, 8)
+        rot = self._dev(launch["rotation"], torch.float64, np.float64).reshape(-1, 9)
+        trans = self._dev(launch["translation"], torch.float64, np.float64).reshape(-1, 3)
+        num_pairs, total = int(off1.numel()), int(idx.shape[0])
+        if not (off2.numel() == num_pairs and moff.numel() == num_pairs + 1 and intr.shape[0] == num_pairs and rot.shape[0] == num_pairs
+                and trans.shape[0] == num_pairs and mask.numel() == total and (count is None or count.numel() == num_pairs)):
+            raise ValueError("the launch's arrays do not agree on the number of pairs / matches")
+        nan = float("nan")
+        out = {"rotation": torch.full((num_pairs, 3, 3), nan, dtype=torch.float64, device=self.device),
+               "translation": torch.full((num_pairs, 3), nan, dtype=torch.float64, device=self.device),
+               "valid_mask": torch.zeros(total, dtype=torch.uint8, device=self.device),
+               "point": torch.full((total, 3), nan, dtype=torch.float64, device=self.device),
+               "cost": torch.full((num_pairs, 2), nan, dtype=torch.float64, device=self.device)}
+        stats = torch.zeros((num_pairs, 8), dtype=torch.int32, device=self.device)
+        if num_pairs:
+            ws = self._workspace(num_pairs, total)
+            ptr = self._L.ptr
+            rc = self._lib.gtsfm_two_view_ba_f64(
+                ptr(kp) if total else None, off1.data_ptr(), off2.data_ptr(), ptr(idx) if total else None, moff.data_ptr(), ptr(count), total,
+                ptr(mask) if total else None, intr.data_ptr(), rot.data_ptr(), trans.data_ptr(), num_pairs, int(opt.max_iterations),
+                float(opt.reproj_error_threshold), float(opt.huber_k), float(opt.measurement_sigma), float(opt.pose_prior_sigma), float(opt.point_prior_sigma),
+                int(opt.min_verified), int(bool(opt.allow_indeterminate)), float(opt.triangulation_threshold), float(opt.triangulation_min_angle_deg),
+                ws.data_ptr(), ws.numel(), out["rotation"].data_ptr(), out["translation"].data_ptr(), ptr(out["valid_mask"]) if total else None,
+                ptr(out["point"]) if total else None, out["cost"].data_ptr(), stats.data_ptr(), torch.cuda.current_stream(self.device).cuda_stream)
+            self._L.check(rc, "gtsfm_two_view_ba_f64")
+        out["stats"] = stats.cpu().numpy()
+        return out

@@ -685,6 +685,46 @@ int gtsfm_triangulate_tracks_f64(const long long* track_off_dev, const int32_t* 
                                  size_t workspace_bytes, double* point_dev, double* avg_error_dev, int32_t* exit_code_dev, uint8_t* inlier_mask_dev,
                                  int32_t* stats_dev, void* stream);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * Two-view bundle adjustment (float64)
+ *   replaces gtsfm/two_view_estimator.py:212-288 (TwoViewEstimator.bundle_adjust: triangulate_two_view_correspondences :165-210, the
+ *   factor graph and Levenberg-Marquardt of gtsfm/bundle/two_view_ba.py / bundle_adjustment.py, the reprojection-error filter of
+ *   gtsfm/common/gtsfm_data.py:839-852), called per pair from run_2view :411-426.
+ * PARITY UNPINNED towards gtsam: its Levenberg-Marquardt path and retraction, the cheirality convention, the pivot thresholds of the
+ * indeterminate-system test, calibrations held fixed (the reference's priors on them have sigma 1e-5) and no pose priors; the
+ * specification is tests/two_view_ba_reference.py.
+ * status: 0 OK, 1 SKIPPED (fewer verified correspondences than min_verified: the verifier's result passes through), 2 NO_INITIAL_POSE
+ * (NaN pose: NaN out, the verifier's mask passes through), 3 NONE_TRIANGULATED (the initial pose, an empty mask), 4 INDETERMINATE
+ * (NaN pose and an empty mask unless allow_indeterminate). A pair's outputs depend on its own data (the places of its verified rows within
+ * its slice included) and the options only, byte for byte.
+ * ---------------------------------------------------------------------------------------------------------- */
+
+/* Bytes of device workspace (0 for sizes out of range): about 120 per match row, the two-measurement tracks and their triangulation. */
+size_t gtsfm_two_view_ba_workspace_bytes(long long num_pairs, long long total_matches);
+
+/* The verifier's arrays where they lie (see gtsfm_verify_essential_f64): kp_xy_dev, kp_off1_dev / kp_off2_dev [num_pairs], match_idx_dev
+ * [total_matches][2], match_off_dev [num_pairs + 1], match_count_dev [num_pairs] (optional, capacity layout), inlier_mask_dev
+ * [total_matches], intrinsics_dev [num_pairs][8], rotation_dev [num_pairs][9] i2Ri1 and translation_dev [num_pairs][3] i2Ui1.
+ * PRECONDITION, as for the verifier: a verified row below match_count_dev names keypoints inside the tables (the call has no table sizes
+ * to check them against; a negative index leaves the row without cameras, rows at or past match_count_dev are never read).
+ * Options: max_iterations accepted steps at most; reproj_error_threshold of the filter in pixels; huber_k (infinity: no robust loss);
+ * the sigmas of the measurements (pixels), the pose prior on the pair's first camera and the point prior on its first point; min_verified
+ * (InlierSupportProcessor's min_num_inliers_est_model); triangulation_threshold / triangulation_min_angle_deg: the TriangulationOptions
+ * of the two-view triangulation (NO_RANSAC), done by gtsfm_triangulate_tracks_f64 itself on two-measurement tracks.
+ * Outputs per pair: rotation_out_dev [9] and unit translation_out_dev [3]; cost_dev [2] (initial, final; NaN unless adjusted);
+ * stats_dev [8] int32 = status, verified, triangulated, valid, accepted steps, linear solves tried, 0, 0. Per match row of a pair's
+ * slice: valid_mask_dev (1 = verified, triangulated and both reprojection errors under the threshold; the verifier's rows, so that
+ * gtsfm_tracks_from_matches takes it in place of inlier_mask_dev) and point_dev [3] (NaN unless triangulated). Rows outside every
+ * pair's slice are not written. The call waits for the stream; match_off_dev not ascending within 0 .. total_matches is
+ * GTSFM_ERR_INVALID. */
+int gtsfm_two_view_ba_f64(const float* kp_xy_dev, const long long* kp_off1_dev, const long long* kp_off2_dev, const int32_t* match_idx_dev,
+                          const long long* match_off_dev, const int32_t* match_count_dev, long long total_matches, const uint8_t* inlier_mask_dev,
+                          const double* intrinsics_dev, const double* rotation_dev, const double* translation_dev, int num_pairs, int max_iterations,
+                          double reproj_error_threshold, double huber_k, double measurement_sigma, double pose_prior_sigma, double point_prior_sigma,
+                          int min_verified, int allow_indeterminate, double triangulation_threshold, double triangulation_min_angle_deg,
+                          void* workspace_dev, size_t workspace_bytes, double* rotation_out_dev, double* translation_out_dev, uint8_t* valid_mask_dev,
+                          double* point_dev, double* cost_dev, int32_t* stats_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

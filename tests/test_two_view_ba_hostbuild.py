@@ -1,0 +1,107 @@
+"""CPU: the two-view bundle adjustment kernels' own arithmetic (the TVBA_HD functions of gtsfm_amd/csrc/two_view_ba_kernels.hip, lane
+loops and lane-0 decisions included), compiled for the host into the stand-alone program tools/two_view_ba_host_main.cpp -- once plain and
+once with the host's address and undefined-behaviour sanitizers -- and held to the rule the device is held to
+(tests/test_two_view_ba_gpu.py, against the live restatement). The program itself requires its two lane partitions to give byte-equal
+outputs: ONE lane that walks each pair's rows in row order and adds every point into the slot of the lane that owns it on the device
+(row j -> slot j % 256) over zeroed memory, against the device's 256 lanes per pair, each with the kernel's own lane loop, run in
+descending order over memory filled with 0xFF; both combine the 256 slots by the device's tree, which defines the sum. No GPU is
+involved."""
+
+import os
+import shutil
+import struct
+import subprocess
+
+import numpy as np
+import pytest
+
+from gtsfm_amd.csrc.build import ARCH, HIPCC
+from tests import two_view_ba_reference as ref
+from tests import two_view_ba_scenes as scenes
+from tests.conftest import REPO
+
+pytestmark = pytest.mark.skipif(shutil.which(HIPCC) is None, reason="hipcc is not installed")
+
+SOURCE = REPO / "tools" / "two_view_ba_host_main.cpp"
+FLAGS = [f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-ffp-contract=off", "-Wall", "-Wno-unused-function"]  # gtsfm_amd/csrc/build.py's
+SANITIZE = "-fsanitize=address,undefined"
+MAGIC = 0x3141425657544754
+
+
+@pytest.fixture(scope="module", params=["plain", "sanitized"])
+def program(request, tmp_path_factory):
+    d = tmp_path_factory.mktemp(f"two_view_ba_host_{request.param}")
+    san = request.param == "sanitized"
+    obj, exe = d / "main.o", d / "two_view_ba_host"
+    # the device side ignores the host-only flag; the link step takes it plain
+    subprocess.run([HIPCC, *FLAGS, *(["-Xarch_host", SANITIZE] if san else []), "-c", str(SOURCE), "-o", str(obj)], check=True, capture_output=True, timeout=600)
+    subprocess.run([HIPCC, *([SANITIZE] if san else []), str(obj), "-o", str(exe)], check=True, capture_output=True, timeout=600)
+    return exe, d
+
+
+def run_program(program, layout, expect_status=0, **options):
+    exe, d = program
+    opt = {**ref.DEFAULTS, **options}
+    p, m = len(layout["kp_off1"]), len(layout["match_idx"])
+    path, out_path = d / "scene.bin", d / "out.bin"
+    with open(path, "wb") as f:
+        f.write(struct.pack("<8q", MAGIC, p, m, len(layout["kp_xy"]), opt["max_iterations"], opt["min_verified"], int(opt["allow_indeterminate"]), 1))
+        f.write(struct.pack("<8d", opt["reproj_error_threshold"], opt["huber_k"], opt["measurement_sigma"], opt["pose_prior_sigma"], opt["point_prior_sigma"],
+                            opt["triangulation_threshold"], opt["triangulation_min_angle_deg"], 0.0))
+        for k, dt in (("kp_xy", np.float32), ("kp_off1", np.int64), ("kp_off2", np.int64), ("match_idx", np.int32), ("match_off", np.int64), ("match_count", np.int32),
+                      ("inlier_mask", np.uint8), ("intrinsics", np.float64), ("rotation", np.float64), ("translation", np.float64)):
+            f.write(np.ascontiguousarray(layout[k], dtype=dt).tobytes())
+    out_path.unlink(missing_ok=True)
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0", UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1")
+    done = subprocess.run([str(exe), str(path), str(out_path)], capture_output=True, text=True, timeout=600, env=env)
+    assert done.returncode == expect_status, f"exit status {done.returncode}\n{done.stderr[-3000:]}"
+    assert "runtime error" not in done.stderr and "Sanitizer" not in done.stderr, done.stderr[-3000:]
+    if expect_status:
+        return done.stderr
+    raw = out_path.read_bytes()
+    assert len(raw) % 2 == 0 and raw[: len(raw) // 2] == raw[len(raw) // 2 :], "the two runs differ"
+    out, at = {}, 0
+    for k, dt, n in (("rotation", np.float64, 9 * p), ("translation", np.float64, 3 * p), ("valid_mask", np.uint8, m), ("point", np.float64, 3 * m), ("cost", np.float64, 2 * p),
+                     ("stats", np.int32, 8 * p)):
+        out[k] = np.frombuffer(raw, dtype=dt, count=n, offset=at)
+        at += n * np.dtype(dt).itemsize
+    assert 2 * at == len(raw)
+    out["rotation"], out["translation"], out["point"] = out["rotation"].reshape(p, 3, 3), out["translation"].reshape(p, 3), out["point"].reshape(m, 3)
+    out["cost"], out["stats"] = out["cost"].reshape(p, 2), out["stats"].reshape(p, 8)
+    return out
+
+
+@pytest.fixture(scope="module")
+def scene():
+    from tests.test_two_view_ba_gpu import scene_pairs
+
+    names, pairs = scene_pairs()
+    return {"names": names, "pairs": pairs, "layout": scenes.capacity_layout(pairs)}
+
+
+def test_host_build_against_the_restatement(program, scene):
+    """The GPU suite's rule (tests/test_two_view_ba_gpu.py) for the whole scene: every status, the lane-count boundaries, the door pair.
+    Rows past match_count hold index -1 and a mask of 1: under the sanitizers, reading a keypoint through them is a report."""
+    from tests.test_two_view_ba_gpu import compare_pair, expected_and_tolerance
+
+    if "expected" not in scene:  # shared by the two builds: their outputs are the same bytes
+        entering = run_program(program, scene["layout"], max_iterations=0)["point"]
+        scene["expected"], scene["tolerance"] = expected_and_tolerance(scene["names"], scene["pairs"], scene["layout"], entering)
+        scene["entering"] = entering
+    out = run_program(program, scene["layout"])
+    assert run_program(program, scene["layout"], max_iterations=0)["point"].tobytes() == scene["entering"].tobytes()
+    assert sum(e["non_decisive"] for e in scene["expected"]) <= len(scene["pairs"]) // 16
+    failures = []
+    for p, (name, rows, exp) in enumerate(zip(scene["names"], scene["layout"]["rows"], scene["expected"])):
+        try:
+            compare_pair(name, out, p, rows, exp, scene["tolerance"])
+        except AssertionError as e:
+            failures.append(f"{name}: {e}")
+    assert not failures, "\n".join(failures)
+
+
+def test_host_build_flags_bad_offsets(program, scene):
+    layout = dict(scenes.capacity_layout(scene["pairs"][2:4]))
+    layout["match_off"] = layout["match_off"].copy()
+    layout["match_off"][1] = layout["match_off"][2] + 1
+    run_program(program, layout, expect_status=3)

@@ -1,0 +1,357 @@
+// Stand-alone host build of the two-view bundle adjustment kernels' arithmetic (the TVBA_HD functions of
+// gtsfm_amd/csrc/two_view_ba_kernels.hip, with the TRI_HD functions of triangulation_kernels.hip for the points that enter), for running
+// it on a CPU and under the host sanitizers:
+//
+//   hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off [-Xarch_host -fsanitize=address,undefined] -c tools/two_view_ba_host_main.cpp -o main.o
+//   hipcc [-fsanitize=address,undefined] main.o -o two_view_ba_host
+//   two_view_ba_host scene.bin out.bin
+//
+// scene.bin: int64 {magic, P, M, keypoint rows, max_iterations, min_verified, allow_indeterminate, 1 with match_count}, double {reproj
+// threshold, huber_k, measurement / pose prior / point prior sigma, triangulation threshold, triangulation min angle, 0}, float
+// kp_xy[2 rows], int64 kp_off1[P], kp_off2[P], int32 match_idx[2 M], int64 match_off[P + 1], int32 match_count[P], uint8 inlier_mask[M],
+// double intrinsics[8 P], rotation[9 P], translation[3 P]. out.bin: two copies (see below) of double rotation[9 P], translation[3 P],
+// uint8 valid_mask[M], double point[3 M], cost[2 P], int32 stats[8 P].
+//
+// The stages are the device call's: init -> prepare -> the triangulation call's stages (NO_RANSAC: count, final) -> adjust. They run twice.
+// First with ONE lane doing all the work over a zeroed workspace and zeroed outputs: in the adjust stage it walks a pair's rows in row order
+// and adds each point into the slot of the lane that owns it on the device (row j of the slice -> slot j % 256), using the per-point
+// functions directly. Then with the device's partition over a workspace and outputs filled with 0xFF: 256 lanes per pair, each walking
+// its own rows with the kernel's lane functions, run in descending order. Both combine the 256 slots by the device's tree (the xor
+// butterfly of each wave, then the four waves): a sum over a pair's points is DEFINED by that partition and tree, so the one lane fills
+// the same slots instead of one running sum. The two outputs must be byte-equal (exit status 2 when they are not): the lane functions'
+// row ownership and strides, the order of the lanes and what the memory held must not matter. Exit status 3: match_off does not ascend
+// within 0 .. M; 1: a bad file.
+// Every input array is a heap allocation of its exact size, so a read outside it is a sanitizer report.
+
+#include <stdarg.h>
+#include <stdlib.h>
+#include <string.h>
+
+#include <vector>
+
+#include "../gtsfm_amd/csrc/triangulation_kernels.hip"
+#include "../gtsfm_amd/csrc/two_view_ba_kernels.hip"
+
+void gtsfm_set_error(const char* fmt, ...) {
+    va_list args;
+    va_start(args, fmt);
+    vfprintf(stderr, fmt, args);
+    va_end(args);
+    fputc('\n', stderr);
+}
+
+namespace {
+
+const long long SCENE_MAGIC = 0x3141425657544754ll;  // "TGTWVBA1"
+
+struct Scene {
+    long long num_pairs, total, kp_rows, max_iterations, min_verified, allow_indeterminate, has_count;
+    double reproj, huber_k, sigma, pose_sigma, point_sigma, tri_threshold, tri_angle;
+    float* kp_xy;
+    long long *kp_off1, *kp_off2, *match_off;
+    int *match_idx, *match_count;
+    uint8_t* inlier_mask;
+    double *intrinsics, *rotation, *translation;
+};
+
+template <class T>
+T* read_array(FILE* f, size_t n) {
+    T* p = (T*)malloc(n ? n * sizeof(T) : 1);  // exact size: the sanitizer sees every read past the end
+    if (p && n && fread(p, sizeof(T), n, f) != n) {
+        free(p);
+        return nullptr;
+    }
+    return p;
+}
+
+bool read_scene(const char* path, Scene& s) {
+    FILE* f = fopen(path, "rb");
+    if (!f) return false;
+    long long head[8];
+    double opts[8];
+    bool ok = fread(head, 8, 8, f) == 8 && fread(opts, 8, 8, f) == 8 && head[0] == SCENE_MAGIC && head[1] >= 0 && head[2] >= 0 && head[3] >= 0 &&
+              head[1] < (1ll << 30) && head[2] < (1ll << 30) && head[3] < (1ll << 31);
+    if (ok) {
+        s.num_pairs = head[1], s.total = head[2], s.kp_rows = head[3], s.max_iterations = head[4], s.min_verified = head[5], s.allow_indeterminate = head[6];
+        s.has_count = head[7];
+        s.reproj = opts[0], s.huber_k = opts[1], s.sigma = opts[2], s.pose_sigma = opts[3], s.point_sigma = opts[4], s.tri_threshold = opts[5], s.tri_angle = opts[6];
+        const size_t p = (size_t)s.num_pairs, m = (size_t)s.total;
+        s.kp_xy = read_array<float>(f, 2 * (size_t)s.kp_rows);
+        s.kp_off1 = read_array<long long>(f, p);
+        s.kp_off2 = read_array<long long>(f, p);
+        s.match_idx = read_array<int>(f, 2 * m);
+        s.match_off = read_array<long long>(f, p + 1);
+        s.match_count = read_array<int>(f, p);
+        s.inlier_mask = read_array<uint8_t>(f, m);
+        s.intrinsics = read_array<double>(f, 8 * p);
+        s.rotation = read_array<double>(f, 9 * p);
+        s.translation = read_array<double>(f, 3 * p);
+        ok = s.kp_xy && s.kp_off1 && s.kp_off2 && s.match_idx && s.match_off && s.match_count && s.inlier_mask && s.intrinsics && s.rotation && s.translation;
+    }
+    fclose(f);
+    return ok;
+}
+
+struct Outputs {
+    std::vector<double> rotation, translation, point, cost;
+    std::vector<uint8_t> valid;
+    std::vector<int> stats;
+    Outputs(const Scene& s, int fill) : rotation(9 * s.num_pairs), translation(3 * s.num_pairs), point(3 * s.total), cost(2 * s.num_pairs), valid(s.total), stats(8 * s.num_pairs) {
+        memset(rotation.data(), fill, rotation.size() * 8);
+        memset(translation.data(), fill, translation.size() * 8);
+        memset(point.data(), fill, point.size() * 8);
+        memset(cost.data(), fill, cost.size() * 8);
+        memset(valid.data(), fill, valid.size());
+        memset(stats.data(), fill, stats.size() * 4);
+    }
+    bool same(const Outputs& o) const {
+        auto eq = [](const void* a, const void* b, size_t n) { return n == 0 || memcmp(a, b, n) == 0; };
+        return eq(rotation.data(), o.rotation.data(), rotation.size() * 8) && eq(translation.data(), o.translation.data(), translation.size() * 8) &&
+               eq(point.data(), o.point.data(), point.size() * 8) && eq(cost.data(), o.cost.data(), cost.size() * 8) && eq(valid.data(), o.valid.data(), valid.size()) &&
+               eq(stats.data(), o.stats.data(), stats.size() * 4);
+    }
+    bool write(FILE* f) const {
+        auto put = [&](const void* p, size_t n) { return n == 0 || fwrite(p, 1, n, f) == n; };
+        return put(rotation.data(), rotation.size() * 8) && put(translation.data(), translation.size() * 8) && put(valid.data(), valid.size()) &&
+               put(point.data(), point.size() * 8) && put(cost.data(), cost.size() * 8) && put(stats.data(), stats.size() * 4);
+    }
+};
+
+// tvba_block_sum on the host: lane [TVBA_THREADS][n] -> out [n]
+void block_sum(const std::vector<double>& lane, int n, double* out) {
+    std::vector<double> part(TVBA_WAVES * n);
+    for (int wave = 0; wave < TVBA_WAVES; ++wave)
+        for (int i = 0; i < n; ++i) {
+            double v[64], next[64];
+            for (int l = 0; l < 64; ++l) v[l] = lane[(size_t)(64 * wave + l) * n + i];
+            for (int off = 32; off > 0; off >>= 1) {
+                for (int l = 0; l < 64; ++l) next[l] = v[l] + v[l ^ off];
+                memcpy(v, next, sizeof(v));
+            }
+            part[wave * n + i] = v[0];
+        }
+    for (int i = 0; i < n; ++i) out[i] = tvba_combine_waves(part.data(), n, i);
+}
+
+// the adjust kernel's workgroup for pair p, by one lane or by the device's partition
+void adjust_pair(const Scene& s, const TvbaWorkspace& w, int p, bool device_partition, Outputs& out) {
+    const TvbaOptions opt = {s.huber_k, 1.0 / s.sigma, 1.0 / s.pose_sigma, 1.0 / (s.point_sigma * s.point_sigma)};
+    long long a, count;
+    bool bad;
+    tvba_pair_rows(s.match_off, s.has_count ? s.match_count : nullptr, p, s.total, a, count, bad);
+    const long long owned = bad ? 0 : s.match_off[p + 1] - s.match_off[p];
+    double* point = out.point.data();
+    uint8_t* valid_mask = out.valid.data();
+    int verified = 0, triangulated = 0;
+    long long first = count;
+    for (long long j = 0; j < owned; ++j) {
+        const long long row = a + j;
+        const bool active = j < count && s.inlier_mask[row] != 0;
+        const bool ok = active && w.tri_exit[row] == 0;
+        verified += active ? 1 : 0;
+        triangulated += ok ? 1 : 0;
+        if (ok && j < first) first = j;
+        for (int i = 0; i < 3; ++i) point[3 * row + i] = ok ? w.tri_point[3 * row + i] : NAN;
+        valid_mask[row] = 0;
+    }
+    const double *r_in = s.rotation + 9 * (size_t)p, *t_in = s.translation + 3 * (size_t)p;
+    bool finite = true;
+    for (int i = 0; i < 9; ++i) finite = finite && isfinite(r_in[i]);
+    for (int i = 0; i < 3; ++i) finite = finite && isfinite(t_in[i]);
+    int status = TVBA_OK;
+    if (verified < s.min_verified) status = TVBA_SKIPPED;
+    else if (!finite) status = TVBA_NO_INITIAL_POSE;
+    else if (triangulated == 0) status = TVBA_NONE_TRIANGULATED;
+    int* st = out.stats.data() + 8 * (size_t)p;
+    for (int i = 0; i < 8; ++i) st[i] = 0;
+    st[1] = verified;
+    st[2] = triangulated;
+    if (status != TVBA_OK) {
+        const bool keep_pose = status != TVBA_NO_INITIAL_POSE, keep_rows = status != TVBA_NONE_TRIANGULATED;
+        for (long long j = 0; j < owned; ++j) {
+            const long long row = a + j;
+            valid_mask[row] = keep_rows && j < count && s.inlier_mask[row] != 0 ? 1 : 0;
+            point[3 * row] = point[3 * row + 1] = point[3 * row + 2] = NAN;
+        }
+        for (int i = 0; i < 9; ++i) out.rotation[9 * (size_t)p + i] = keep_pose ? r_in[i] : NAN;
+        for (int i = 0; i < 3; ++i) out.translation[3 * (size_t)p + i] = keep_pose ? t_in[i] : NAN;
+        out.cost[2 * (size_t)p] = out.cost[2 * (size_t)p + 1] = NAN;
+        st[0] = status;
+        st[2] = status == TVBA_SKIPPED ? 0 : triangulated;  // the reference does not triangulate a pair it skips
+        st[3] = keep_rows ? verified : 0;
+        return;
+    }
+    TvbaPair q;
+    q.a = a, q.count = count, q.first_row = a + first, q.inlier_mask = s.inlier_mask, q.tri_exit = w.tri_exit, q.uv = w.uv, q.opt = opt;
+    const double* k = s.intrinsics + 8 * (size_t)p;
+    q.cal[0] = {k[0], k[1], k[2], k[3]};
+    q.cal[1] = {k[4], k[5], k[6], k[7]};
+    for (int i = 0; i < 3; ++i) q.prior_at[i] = w.tri_point[3 * q.first_row + i];
+
+    TvbaPose pose[2], trial_pose[2];
+    TvbaControl ctl;
+    double sum[TVBA_SUMS], low[144], rhs[12], dc[12];
+    std::vector<double> lanes((size_t)TVBA_THREADS * TVBA_SUMS);
+    // device_partition: 256 lanes, each walking its own rows (tvba_lane_*), run in descending order. Otherwise ONE lane walks the pair's rows in
+    // row order and adds each point into the slot of the lane that owns it on the device (row j -> slot j % 256): the same 256 per-lane sums
+    // only if the ownership and the per-point functions are what the lane loops use.
+    auto each_lane = [&](auto&& body) {
+        for (int n = TVBA_THREADS - 1; n >= 0; --n) body(n);
+    };
+    auto each_row = [&](auto&& body) {
+        for (long long j = 0; j < q.count; ++j)
+            if (q.takes_part(q.a + j)) body(q.a + j, (int)(j % TVBA_THREADS));
+    };
+    auto total_cost = [&](const TvbaPose* at, const double* values) {
+        if (device_partition) {
+            each_lane([&](int lane) { lanes[lane] = tvba_lane_cost(q, lane, at, values); });
+        } else {
+            for (int n = 0; n < TVBA_THREADS; ++n) lanes[n] = 0.0;
+            each_row([&](long long row, int slot) {
+                lanes[slot] = lanes[slot] + tvba_point_cost(at, q.cal, values + 3 * row, q.uv + 4 * row, q.uv + 4 * row + 2, q.prior(row), q.opt);
+            });
+        }
+        block_sum(lanes, 1, sum);
+        return sum[0] + tvba_pose_prior(at[0], opt.pose_prior_inv_sigma, nullptr);
+    };
+    auto reduced_system = [&](double lam) {
+        if (device_partition) {
+            each_lane([&](int lane) { tvba_lane_reduce(q, lane, pose, point, lam, lanes.data() + (size_t)lane * TVBA_SUMS); });
+        } else {
+            bool ok[TVBA_THREADS];
+            for (int n = 0; n < TVBA_THREADS; ++n) ok[n] = true;
+            for (size_t i = 0; i < (size_t)TVBA_THREADS * TVBA_SUMS; ++i) lanes[i] = 0.0;
+            each_row([&](long long row, int slot) {
+                ok[slot] = tvba_point_reduce(pose, q.cal, point + 3 * row, q.uv + 4 * row, q.uv + 4 * row + 2, q.prior(row), q.opt, lam, lanes.data() + (size_t)slot * TVBA_SUMS) && ok[slot];
+            });
+            for (int n = 0; n < TVBA_THREADS; ++n)
+                if (!ok[n]) lanes[(size_t)n * TVBA_SUMS] = NAN;
+        }
+        block_sum(lanes, TVBA_SUMS, sum);
+    };
+    auto step_points = [&](double lam) {
+        if (device_partition) {
+            each_lane([&](int lane) { tvba_lane_step(q, lane, pose, point, lam, dc, w.trial, lanes.data() + 2 * (size_t)lane); });
+        } else {
+            for (int n = 0; n < 2 * TVBA_THREADS; ++n) lanes[n] = 0.0;
+            each_row([&](long long row, int slot) {
+                double dp[3], gtd;
+                tvba_point_step(pose, q.cal, point + 3 * row, q.uv + 4 * row, q.uv + 4 * row + 2, q.prior(row), q.opt, lam, dc, dp, gtd);
+                for (int i = 0; i < 3; ++i) w.trial[3 * row + i] = point[3 * row + i] + dp[i];
+                lanes[2 * slot] = lanes[2 * slot] + gtd;
+                lanes[2 * slot + 1] = lanes[2 * slot + 1] + (dp[0] * dp[0] + dp[1] * dp[1] + dp[2] * dp[2]);
+            });
+        }
+        block_sum(lanes, 2, sum);
+    };
+    auto accept_points = [&]() {
+        if (device_partition) each_lane([&](int lane) { tvba_lane_accept(q, lane, point, w.trial); });
+        else each_row([&](long long row, int) { for (int i = 0; i < 3; ++i) point[3 * row + i] = w.trial[3 * row + i]; });
+    };
+    tvba_initial_poses(r_in, t_in, pose);
+    ctl.lam = TVBA_LAMBDA_INITIAL;
+    ctl.accepted = ctl.solves = ctl.stop = ctl.solved = ctl.accept = 0;
+    ctl.cost = ctl.first_cost = total_cost(pose, point);
+    while (ctl.accepted < s.max_iterations && !ctl.stop) {
+        const double lam = ctl.lam;
+        reduced_system(lam);
+        tvba_solve_trial(ctl, sum, opt.pose_prior_inv_sigma, pose, trial_pose, low, rhs, dc);
+        double gtd = 0.0, dd = 0.0, fresh = NAN;
+        if (ctl.solved) {
+            for (int i = 0; i < 12; ++i) {
+                gtd = gtd + sum[78 + i] * dc[i];
+                dd = dd + dc[i] * dc[i];
+            }
+            step_points(lam);
+            gtd = gtd + sum[0];
+            dd = dd + sum[1];
+            fresh = total_cost(trial_pose, w.trial);
+        }
+        tvba_decide(ctl, gtd, dd, fresh, pose, trial_pose);
+        if (ctl.accept) accept_points();
+    }
+    reduced_system(0.0);
+    tvba_pose_prior(pose[0], opt.pose_prior_inv_sigma, sum);
+    const bool indeterminate = !tvba_cholesky12(sum, 0.0, nullptr, low, nullptr);
+    const bool give_up = indeterminate && !s.allow_indeterminate;
+    int valid = 0;
+    if (!give_up && device_partition) each_lane([&](int lane) { valid += tvba_lane_filter(q, lane, pose, point, s.reproj, valid_mask); });
+    if (!give_up && !device_partition)
+        each_row([&](long long row, int) {
+            const double e1 = tvba_error(pose[0], q.cal[0], point + 3 * row, (double)q.uv[4 * row], (double)q.uv[4 * row + 1]);
+            const double e2 = tvba_error(pose[1], q.cal[1], point + 3 * row, (double)q.uv[4 * row + 2], (double)q.uv[4 * row + 3]);
+            valid_mask[row] = e1 < s.reproj && e2 < s.reproj ? 1 : 0;
+            valid += valid_mask[row];
+        });
+    tvba_relative_pose(pose, give_up, out.rotation.data() + 9 * (size_t)p, out.translation.data() + 3 * (size_t)p);
+    out.cost[2 * (size_t)p] = ctl.first_cost;
+    out.cost[2 * (size_t)p + 1] = ctl.cost;
+    st[0] = indeterminate ? TVBA_INDETERMINATE : TVBA_OK;
+    st[3] = valid;
+    st[4] = ctl.accepted;
+    st[5] = ctl.solves;
+}
+
+// 0, or the error flag's exit status
+int run(const Scene& s, bool second, Outputs& out) {
+    const size_t bytes = tvba_layout(nullptr, s.num_pairs, s.total).bytes;
+    void* base = aligned_alloc(256, bytes);
+    if (!base) return 1;
+    memset(base, second ? 0xFF : 0x00, bytes);
+    const TvbaWorkspace w = tvba_layout(base, s.num_pairs, s.total);
+    memset(w.flags, 0, 16);
+    const int lanes = second ? TVBA_THREADS : 1;
+    for (int lane = 0; lane < lanes; ++lane) tvba_init_rows(lane, lanes, s.total, w.track_off, w.image, w.uv);
+    for (int p = 0; p < (int)s.num_pairs; ++p)
+        for (int n = 0; n < lanes; ++n)
+            tvba_prepare_pair(p, second ? lanes - 1 - n : n, lanes, s.kp_xy, s.kp_off1, s.kp_off2, s.match_idx, s.match_off, s.has_count ? s.match_count : nullptr,
+                              s.inlier_mask, s.total, s.intrinsics, s.rotation, s.translation, w.image, w.uv, w.cams, w.flags);
+    if (s.total > 0) {  // gtsfm_triangulate_tracks_f64 with NO_RANSAC: count, (scan of zeros), final
+        const TriWorkspace t = tri_layout(w.tri_ws, s.total, 2 * s.total, 0);
+        memset(t.flags, 0, 16);
+        for (long long j = 0; j < s.total; ++j) tri_count_track(j, w.track_off, s.total, 2 * s.total, TRI_NO_RANSAC, 0, t.hyp_off, t.flags);
+        t.hyp_off[s.total] = 0;
+        for (long long j = 0; j < s.total; ++j)
+            tri_final_track(j, w.track_off, w.image, w.uv, s.total, w.cams, 2 * (int)s.num_pairs, TRI_NO_RANSAC, s.tri_threshold, s.tri_angle, t.hyp_off, t.hyp, t.cap,
+                            t.flags, w.tri_point, w.tri_avg, w.tri_exit, w.tri_mask, w.tri_stats);
+    }
+    for (int p = 0; p < (int)s.num_pairs; ++p) adjust_pair(s, w, p, second, out);
+    const int status = w.flags[0] ? 3 : 0;
+    free(base);
+    return status;
+}
+
+}  // namespace
+
+int main(int argc, char** argv) {
+    if (argc != 3) {
+        fprintf(stderr, "usage: %s scene.bin out.bin\n", argv[0]);
+        return 1;
+    }
+    Scene s;
+    if (!read_scene(argv[1], s)) {
+        fprintf(stderr, "%s: not a scene file\n", argv[1]);
+        return 1;
+    }
+    if (s.max_iterations < 0 || !(s.reproj > 0.0) || !(s.huber_k > 0.0) || !(s.sigma > 0.0) || !(s.pose_sigma > 0.0) || !(s.point_sigma > 0.0) ||
+        !(s.tri_threshold > 0.0) || s.tri_angle != s.tri_angle) {
+        fprintf(stderr, "%s: options outside the device call's domain\n", argv[1]);
+        return 1;
+    }
+    Outputs first(s, 0x00), second(s, 0xFF);
+    int status = run(s, false, first);
+    const int other = run(s, true, second);
+    if (status != other) status = 2;
+    if (status == 0 && !first.same(second)) {
+        fprintf(stderr, "the outputs depend on the order of the lanes or on what the memory held\n");
+        status = 2;
+    }
+    if (status == 0) {
+        FILE* f = fopen(argv[2], "wb");
+        if (!f || !first.write(f) || !second.write(f)) status = 1;
+        if (f) fclose(f);
+    }
+    free(s.kp_xy), free(s.kp_off1), free(s.kp_off2), free(s.match_idx), free(s.match_off), free(s.match_count), free(s.inlier_mask), free(s.intrinsics);
+    free(s.rotation), free(s.translation);
+    return status;
+}
