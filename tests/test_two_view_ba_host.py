@@ -293,3 +293,122 @@ def test_two_view_config_instantiates_and_pickles():
     assert est._ba_optimizer.options() == opts.optimizer().options()
     assert {k: getattr(est._ba_optimizer.options(), k) for k in ref.DEFAULTS} == ref.DEFAULTS
     assert est._triangulation_settings() == (math.inf, 0.0)
+
+
+# ---- the catalogue of hard pairs (tests/two_view_ba_scenes.py: hard_pairs): every family contains what it is named for
+
+
+@pytest.fixture(scope="module")
+def hard_runs():
+    """family -> [(entry, the restatement's result from its own triangulation, the layout the device gets)]"""
+    out = {}
+    with np.errstate(over="ignore", invalid="ignore"):
+        for family, entries in scenes.hard_pairs().items():
+            out[family] = []
+            for e in entries:
+                p = e["pair"]
+                out[family].append((e, ref.two_view_ba(p["k1"], p["k2"], p["uv1"], p["uv2"], p["R"], p["t"], **e["options"]), scenes.capacity_layout([p])))
+    return out
+
+
+def _rejected(res):
+    return sum(res["rejected"].values())
+
+
+def _first_slice_row(res, layout):
+    """where in its slice (hence in which lane and stride) the pair's first triangulated row lies"""
+    return int(layout["rows"][0][np.flatnonzero(res["triangulated"])[0]] - layout["match_off"][0])
+
+
+def test_hard_families_are_decisive_or_say_so(hard_runs):
+    assert tuple(hard_runs) == scenes.HARD_FAMILIES and scenes.DECISIVE_FAMILIES == scenes.HARD_FAMILIES[:-1]
+    for family, runs in hard_runs.items():
+        for e, res, _ in runs:
+            print(f"{family}/{e['name']}: {ref.STATUS_NAMES[res['status']]} stats {res['stats'][:6].tolist()} stop {res['stop']} rejected "
+                  f"{ {k: v for k, v in res['rejected'].items() if v} } non-decisive {res['non_decisive']}")
+            assert res["status"] in (ref.OK, ref.INDETERMINATE) and res["stop"] in ref.STOP_REASONS and _rejected(res) == res["stats"][5] - res["stats"][4]
+            assert res["non_decisive"] == (family == "non_decisive"), f"{family}/{e['name']}"
+            if family != "strides" and family != "late_first" and e["name"] not in ("far_n300", "far_n600"):
+                assert len(e["pair"]["uv1"]) <= 64, "a pair larger than one wave outside the families about lane strides"
+
+
+def test_hard_family_rejections(hard_runs):
+    runs = hard_runs["rejections"]
+    assert sum(_rejected(res) >= 10 for _, res, _ in runs) >= 4
+    for e, res, _ in runs:
+        assert res["status"] == ref.OK and res["stop"] == "tolerance" and _rejected(res) == res["rejected"]["fidelity"] > 0, e["name"]
+    sizes = {len(e["pair"]["uv1"]) for e, _, _ in runs}
+    assert {300, 600} <= sizes and any(e["name"].startswith("displaced") for e, _, _ in runs)
+
+
+def test_hard_family_step_limit(hard_runs):
+    by_name = {e["name"]: res for e, res, _ in hard_runs["step_limit"]}
+    for name, steps in (("limit_1", 1), ("limit_2", 2), ("limit_3", 3), ("limit_4", 4), ("behind_limit_5", 5), ("displaced_100", 100)):
+        res = by_name[name]
+        assert res["stop"] == "step_limit" and res["stats"][4] == steps < res["stats"][5], name  # the limit counts accepted steps, not solves
+    assert by_name["limit_1"]["rejected"]["fidelity"] >= 2 and by_name["displaced_100"]["stats"][5] > 100
+    # the first solves are the rejected ones: one step more costs exactly one solve more
+    assert by_name["limit_2"]["stats"][5] == by_name["limit_1"]["stats"][5] + 1 and by_name["limit_3"]["stats"][5] == by_name["limit_1"]["stats"][5] + 2
+
+
+def test_hard_family_late_first(hard_runs):
+    rows = {e["name"]: (_first_slice_row(res, lay), res) for e, res, lay in hard_runs["late_first"]}
+    assert rows["second_stride_91"][0] >= 256 and rows["second_stride_92"][0] >= 256  # the prior's row in a second stride
+    assert 0 < rows["other_lane"][0] < 256 and rows["other_lane"][0] % 64 != 0  # in the first stride, not lane 0 of any wave
+    for name, (_, res) in rows.items():
+        assert res["status"] == ref.OK and 1 < res["stats"][2] < res["stats"][1] and res["stats"][4] >= 2, name
+    assert int(np.flatnonzero(rows["second_stride_91"][1]["triangulated"])[0]) == 270
+
+
+def test_hard_family_triangulation_options(hard_runs):
+    for e, res, _ in hard_runs["triangulation_options"]:
+        p = e["pair"]
+        free = ref.two_view_ba(p["k1"], p["k2"], p["uv1"], p["uv2"], p["R"], p["t"], max_iterations=0)
+        print(e["name"], "triangulated", res["stats"][2], "of", res["stats"][1], "; without the option", free["stats"][2])
+        assert res["status"] == ref.OK and res["stats"][4] >= 2
+        if e["name"] == "min_angle_1":  # the option is passed and lets every point through: the other side of its test
+            assert res["stats"][2] == free["stats"][2] == 40
+        else:
+            assert 15 <= res["stats"][2] <= 32 < free["stats"][2]
+
+
+def test_hard_family_geometry_loss_and_strides(hard_runs):
+    for family in ("geometry", "loss", "strides"):
+        for e, res, _ in hard_runs[family]:
+            assert res["status"] == ref.OK and res["stats"][4] >= 2 and res["stats"][2] == res["stats"][1], (family, e["name"])
+    by_name = {e["name"]: (e, res) for family in ("geometry", "loss", "strides") for e, res, _ in hard_runs[family]}
+    assert by_name["no_filter"][1]["valid"].all() and not by_name["sigma_0.5"][1]["valid"].all()
+    assert abs(np.linalg.norm(by_name["translation_x5"][0]["pair"]["t"]) - 5.0) < 1e-12 and abs(np.linalg.norm(by_name["translation_x1e-3"][0]["pair"]["t"]) - 1e-3) < 1e-15
+    pair = by_name["roll"][0]["pair"]
+    assert abs(np.degrees(np.arccos((np.trace(pair["R_true"]) - 1) / 2)) - np.degrees(3.1)) < 1e-6
+    # both Huber branches at k = 0.1, at the values the run ends on (every point triangulates, so the state's rows are the pair's)
+    entry, res = by_name["huber_0.1"]
+    e_norm = ref._huber(ref._measure(res["state"], 1, entry["pair"]["k2"], entry["pair"]["uv2"].astype(np.float64))[2], 0.1)[0]
+    assert (e_norm <= 0.1).any() and (e_norm > 0.1).any()
+    assert len(by_name["n1100"][0]["pair"]["uv1"]) == 1100  # with its unverified rows: a slice of 1431 rows, six strides, the last ragged
+
+
+def test_hard_family_non_finite(hard_runs):
+    """Every comparison the loop makes on this pair has an operand that is not finite, so the pair is decisive although its final pivots are 0."""
+    for e, res, _ in hard_runs["non_finite"]:
+        assert res["status"] == ref.INDETERMINATE and not res["non_decisive"] and res["stop"] == "lambda_bound", e["name"]
+        assert res["stats"][4] == 0 and res["stats"][5] == 11 and res["rejected"]["cost_not_finite"] == 11 and np.isposinf(res["cost"]).all(), e["name"]
+        assert not [m for m in res["margins"] if m[0] != "filter"], e["name"]
+        if e["options"].get("allow_indeterminate"):
+            np.testing.assert_array_equal(res["rotation"], e["pair"]["R"])
+            np.testing.assert_allclose(res["translation"], e["pair"]["t"], rtol=0, atol=4e-15)
+            assert res["valid"].any() and not res["valid"].all()
+        else:
+            assert np.isnan(res["rotation"]).all() and np.isnan(res["translation"]).all() and not res["valid"].any()
+
+
+def test_pivot_margins_of_the_loop():
+    """A damped factorisation inside the loop enters the margins (a pair whose in-loop factorisation hangs on a rounding-level pivot is not
+    decisive), and a diagonal that is not finite does not widen the band."""
+    pair = scenes.make_pair(102, 15)
+    res = ref.two_view_ba(pair["k1"], pair["k2"], pair["uv1"], pair["uv2"], pair["R"], pair["t"])
+    assert sum(name == "pivot" for name, _, _ in res["margins"]) == res["stats"][5] + 1
+    u = np.diag([np.inf, 4.0, np.nan])
+    assert ref.pivot_margin(np.array([[1.0, 2.0, np.nan]]), np.array([3.0]), u, 1e-10) == ("pivot", 1.0, 4e-10)
+    assert ref.pivot_margin(np.array([[np.nan, np.inf, np.nan]]), np.array([np.nan]), u, 1e-10) is None
+    assert ref.pivot_margin(np.array([[0.0, 1.0, 1.0], [2.0, 2.0, 2.0]]), np.array([1e-30]), np.eye(3), 1e-10, np.array([True, False])) == ("pivot", 2.0, 1e-10)

@@ -39,7 +39,8 @@ def program(request, tmp_path_factory):
     return exe, d
 
 
-def run_program(program, layout, expect_status=0, **options):
+def run_program(program, layout, expect_status=0, trace=False, **options):
+    """``trace``: also ``out["trace"]``, the lines of the program's trace of rejected trials and stops."""
     exe, d = program
     opt = {**ref.DEFAULTS, **options}
     p, m = len(layout["kp_off1"]), len(layout["match_idx"])
@@ -53,7 +54,7 @@ def run_program(program, layout, expect_status=0, **options):
             f.write(np.ascontiguousarray(layout[k], dtype=dt).tobytes())
     out_path.unlink(missing_ok=True)
     env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0", UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1")
-    done = subprocess.run([str(exe), str(path), str(out_path)], capture_output=True, text=True, timeout=600, env=env)
+    done = subprocess.run([str(exe), str(path), str(out_path), *([str(d / "trace.txt")] if trace else [])], capture_output=True, text=True, timeout=600, env=env)
     assert done.returncode == expect_status, f"exit status {done.returncode}\n{done.stderr[-3000:]}"
     assert "runtime error" not in done.stderr and "Sanitizer" not in done.stderr, done.stderr[-3000:]
     if expect_status:
@@ -68,6 +69,8 @@ def run_program(program, layout, expect_status=0, **options):
     assert 2 * at == len(raw)
     out["rotation"], out["translation"], out["point"] = out["rotation"].reshape(p, 3, 3), out["translation"].reshape(p, 3), out["point"].reshape(m, 3)
     out["cost"], out["stats"] = out["cost"].reshape(p, 2), out["stats"].reshape(p, 8)
+    if trace:
+        out["trace"] = [line.split() for line in (d / "trace.txt").read_text().splitlines()]
     return out
 
 
@@ -105,3 +108,53 @@ def test_host_build_flags_bad_offsets(program, scene):
     layout["match_off"] = layout["match_off"].copy()
     layout["match_off"][1] = layout["match_off"][2] + 1
     run_program(program, layout, expect_status=3)
+
+
+# ---- the catalogue of hard pairs: proven here before a GPU sees it
+
+HARD_CACHE = {}  # the restatement runs, shared by the two builds: their entering points are the same bytes
+
+
+@pytest.fixture(scope="module")
+def hard():
+    return scenes.hard_pairs()
+
+
+@pytest.mark.parametrize("family", scenes.HARD_FAMILIES)
+def test_host_build_hard_family(program, hard, family):
+    """tests/test_two_view_ba_gpu.py's rule for one family of the catalogue, the tolerance measured on that family."""
+    from tests.test_two_view_ba_gpu import check_non_finite_family, run_family
+
+    records = run_family(lambda layout, **o: run_program(program, layout, **o), family, hard[family], cache=HARD_CACHE)
+    if family == "non_finite":
+        check_non_finite_family(records)
+
+
+def test_host_build_dud_rows(program, hard):
+    """A verified row without a keypoint index or with a NaN pixel: under the sanitizers, reading a keypoint through index -1 is a report."""
+    from tests.test_two_view_ba_gpu import check_dud_rows
+
+    run = lambda layout, **o: run_program(program, layout, **o)  # noqa: E731
+    check_dud_rows(run, hard["rejections"][0]["pair"])
+    check_dud_rows(run, scenes.make_pair(102, 14), verified_decides=True)
+
+
+def test_host_build_rejection_routes(program, hard):
+    """Which way each rejected trial goes in the kernel's arithmetic, from the program's trace. On the non-finite pair the restatement
+    rejects all 11 trials by a trial cost that is not finite (its weights k / inf = 0 are applied first, so its blocks are exact zeros and its
+    step is zero); the kernel's arithmetic applies the weight last, 0 x inf = NaN poisons the sums, and all 11 go by the failed solve. Only
+    the discrete outputs have to agree, and do (test_host_build_hard_family). A far start is rejected by the fidelity test in both."""
+    entry = hard["non_finite"][0]
+    out = run_program(program, scenes.capacity_layout([entry["pair"]]), trace=True, **entry["options"])
+    print("non_finite:", out["trace"])
+    assert [line[3] for line in out["trace"][:-1]] == ["poisoned"] * 11 and out["trace"][-1] == ["0", "stop", "lambda_bound"]
+    assert float(out["trace"][0][2]) == ref.LAMBDA_INITIAL
+    assert float(out["trace"][-2][2]) <= ref.LAMBDA_UPPER < float(out["trace"][-2][2]) * ref.LAMBDA_FACTOR
+    entry = hard["rejections"][0]
+    layout = scenes.capacity_layout([entry["pair"]])
+    out = run_program(program, layout, trace=True)
+    entering = run_program(program, layout, max_iterations=0)["point"]
+    pair = entry["pair"]
+    exp = ref.two_view_ba(pair["k1"], pair["k2"], pair["uv1"], pair["uv2"], pair["R"], pair["t"], initial_points=entering[layout["rows"][0]])
+    assert not exp["non_decisive"] and exp["rejected"]["fidelity"] == sum(exp["rejected"].values()) >= 10
+    assert [line[3] for line in out["trace"][:-1]] == ["fidelity"] * exp["rejected"]["fidelity"] and out["trace"][-1] == ["0", "stop", exp["stop"]]

@@ -27,8 +27,13 @@ PARITY UNPINNED towards gtsam -- every item below is restated from gtsam's docum
 Linear algebra, in an order the device can follow: each point's 3 x 3 block is eliminated (elimination without pivoting, written out)
 into the 12 x 12 Schur complement of the cameras, which is factored by a Cholesky written out below; no LAPACK.
 
-A pair is marked NON-DECISIVE when one of its own decisions (a fidelity test, a stopping test, a pivot sign, a reprojection error
-against the filter threshold) lies within ``sensitivity`` of its threshold: another rounding path may decide otherwise.
+A pair is marked NON-DECISIVE when one of its own decisions (a fidelity test, a stopping test, a pivot sign -- of every system factored,
+the damped ones of the loop included --, a reprojection error against the filter threshold) lies within ``sensitivity`` of its threshold:
+another rounding path may decide otherwise. A decision with an operand that is not finite (an infinite cost, a NaN pivot) has no margin: no
+rounding path turns it.
+
+``two_view_ba`` also reports how the loop went: ``stop`` (one of STOP_REASONS) and ``rejected``, the number of trials rejected by each of
+REJECT_ROUTES.
 """
 
 from __future__ import annotations
@@ -51,6 +56,10 @@ MIN_FIDELITY = 1e-3
 ABS_TOL = 1e-5
 REL_TOL = 1e-5
 FILTER_MARGIN_PX = 1e-6  # as the triangulation restatement
+STOP_REASONS = ("tolerance", "lambda_bound", "step_limit")
+# why a trial was rejected, in the order the tests are made: a point block's pivot, a pivot of the reduced camera system, a step that is
+# not finite, a trial cost that is not finite, a model decrease <= 0 (or NaN), a fidelity <= MIN_FIDELITY
+REJECT_ROUTES = ("point_pivot", "camera_pivot", "step_not_finite", "cost_not_finite", "model_not_positive", "fidelity")
 
 DEFAULTS = dict(max_iterations=100, reproj_error_threshold=0.5, huber_k=1.345, measurement_sigma=1.0, pose_prior_sigma=0.1, point_prior_sigma=0.1,
                 min_verified=15, allow_indeterminate=False, triangulation_threshold=math.inf, triangulation_min_angle_deg=0.0)
@@ -110,9 +119,10 @@ def _measure(state: _State, cam: int, k, uv):
 
 def _huber(res, kh):
     dt = res.dtype.type
-    e = np.sqrt(res[:, 0] * res[:, 0] + res[:, 1] * res[:, 1])
-    small = e <= kh
-    loss = np.where(small, e * e * dt(0.5), kh * (e - kh * dt(0.5)))
+    with np.errstate(over="ignore"):  # a scaled residual may overflow: e = inf, loss = inf, weight = k / inf = 0
+        e = np.sqrt(res[:, 0] * res[:, 0] + res[:, 1] * res[:, 1])
+        small = e <= kh
+        loss = np.where(small, e * e * dt(0.5), kh * (e - kh * dt(0.5)))
     w = np.where(small, 1, kh / np.where(small, 1, e))
     return e, loss, w.astype(res.dtype)
 
@@ -200,6 +210,18 @@ def linearise(state: _State, k1, k2, uv1, uv2, p0_init, opt):
     return v, w, gp, u, gc
 
 
+def overflowed_points(state: _State, k1, k2, uv1, uv2, opt):
+    """[n] bool: points with a measurement whose scaled residual norm is not finite (see pivot_margin)."""
+    dt = state.pts.dtype.type
+    out = np.zeros(len(state.pts), bool)
+    for cam, (k, uv) in enumerate(((k1, uv1), (k2, uv2))):
+        _, _, res, _ = _measure(state, cam, k, uv)
+        with np.errstate(over="ignore", invalid="ignore"):
+            e, _, _ = _huber(res / dt(opt["measurement_sigma"]), dt(opt["huber_k"]))
+        out |= ~np.isfinite(e)
+    return out
+
+
 def solve_point_blocks(v, lam, rhs):
     """(V_j + lam I)^-1 rhs_j for every point, rhs [n, 3, m]: elimination without pivoting, written out. Returns (x, pivots [n, 3])."""
     a00, a01, a02 = v[:, 0, 0] + lam, v[:, 0, 1], v[:, 0, 2]
@@ -253,8 +275,28 @@ def cholesky_solve(s, b):
     return x, piv
 
 
+def pivot_margin(ppiv, cpiv, u, sensitivity, overflowed=None):
+    """The margin entry of one factorisation's pivot signs, or None when no pivot is finite. The band scales with the largest FINITE
+    diagonal entry of the cameras' block: an entry that is not finite must not make every pivot look rounding-level.
+    ``overflowed`` [n]: points with a measurement whose scaled residual norm is not finite. Its weight is k / inf = 0 exactly, so its blocks
+    are exact zeros here and 0 x inf = NaN where the weight is applied last (the device): a pivot of 0 there is no rounding-level value,
+    it fails on every path. Such points' pivots, and the pivots of a camera system that such a point entered, get no margin."""
+    ppiv, cpiv = np.asarray(ppiv), np.asarray(cpiv)
+    if overflowed is not None and overflowed.any():
+        ppiv, cpiv = ppiv[~overflowed], cpiv[:0]
+    piv = np.concatenate([ppiv.reshape(-1), cpiv.reshape(-1)]).astype(np.float64)
+    piv = piv[np.isfinite(piv)]
+    if not piv.size:
+        return None
+    diag = np.abs(np.diagonal(u).astype(np.float64))
+    diag = diag[np.isfinite(diag)]
+    scale = float(max(diag.max(initial=0.0), 1.0))
+    return ("pivot", float(np.min(np.abs(piv))), sensitivity * scale)
+
+
 def schur_solve(v, w, gp, u, gc, lam):
-    """The damped step: (dc [12], dp [n, 3]) or None, and the pivots (points [n, 3], cameras [12])."""
+    """The damped step: (dc [12], dp [n, 3]) or None, the pivots (points [n, 3], cameras [12]), and why there is no step (None, or one
+    of the first three REJECT_ROUTES)."""
     dt = v.dtype
     n = len(v)
     rhs = np.concatenate([np.swapaxes(w, 1, 2), gp[:, :, None]], axis=2)  # [n, 3, 13]
@@ -268,10 +310,12 @@ def schur_solve(v, w, gp, u, gc, lam):
             s = s - contrib[j, :, :12]
             b = b + contrib[j, :, 12]
     dc, cpiv = (None, np.full(12, np.nan, dtype=dt)) if bad else cholesky_solve(s, b)
-    if dc is None or not np.isfinite(dc).all():
-        return None, None, ppiv, cpiv
+    if dc is None:
+        return None, None, ppiv, cpiv, "point_pivot" if bad else "camera_pivot"
+    if not np.isfinite(dc).all():
+        return None, None, ppiv, cpiv, "step_not_finite"
     dp = -(y[:, :, 12] + y[:, :, :12] @ dc)
-    return dc, dp, ppiv, cpiv
+    return dc, dp, ppiv, cpiv, None
 
 
 def retract(state: _State, dc, dp) -> _State:
@@ -282,9 +326,11 @@ def retract(state: _State, dc, dp) -> _State:
     return _State(r[0], t[0], r[1], t[1], state.pts + dp)
 
 
-def optimise(state: _State, k1, k2, uv1, uv2, opt, abs_tol=ABS_TOL, rel_tol=REL_TOL, trace: Optional[list] = None, sensitivity: float = 0.0):
+def optimise(state: _State, k1, k2, uv1, uv2, opt, abs_tol=ABS_TOL, rel_tol=REL_TOL, trace: Optional[list] = None, sensitivity: float = 0.0,
+             report: Optional[dict] = None):
     """Levenberg-Marquardt as the header states it. Returns (state, initial cost, final cost, accepted, solves, margins): ``margins`` holds
-    (name, |value - threshold|, band) of every fidelity and stopping decision taken; within the band the decision is not decisive."""
+    (name, |value - threshold|, band) of every fidelity, stopping and pivot-sign decision taken; within the band the decision is not
+    decisive. ``report`` receives ``stop`` and ``rejected`` (see the header)."""
     dt = state.pts.dtype.type
     p0 = state.pts[0].copy()
     cur = cost(state, k1, k2, uv1, uv2, p0, opt)
@@ -292,12 +338,18 @@ def optimise(state: _State, k1, k2, uv1, uv2, opt, abs_tol=ABS_TOL, rel_tol=REL_
     lam = dt(LAMBDA_INITIAL)
     accepted = solves = 0
     margins = []
+    rejected = dict.fromkeys(REJECT_ROUTES, 0)
+    reason = None
     stop = False
     while accepted < opt["max_iterations"] and not stop:
         v, w, gp, u, gc = linearise(state, k1, k2, uv1, uv2, p0, opt)
+        overflowed = overflowed_points(state, k1, k2, uv1, uv2, opt)
         while True:
             solves += 1
-            dc, dp, _, _ = schur_solve(v, w, gp, u, gc, lam)
+            dc, dp, ppiv, cpiv, why = schur_solve(v, w, gp, u, gc, lam)
+            entry = pivot_margin(ppiv, cpiv, u, sensitivity, overflowed)
+            if entry is not None:
+                margins.append(entry)
             ok = False
             if dc is not None:
                 trial = retract(state, dc, dp)
@@ -308,10 +360,16 @@ def optimise(state: _State, k1, k2, uv1, uv2, opt, abs_tol=ABS_TOL, rel_tol=REL_
                     gtd = gtd + gp[j] @ dp[j]
                     dd = dd + dp[j] @ dp[j]
                 model = -dt(0.5) * gtd + dt(0.5) * lam * dd
-                if np.isfinite(new) and model > 0:
+                if not np.isfinite(new):
+                    why = "cost_not_finite"
+                elif not model > 0:
+                    why = "model_not_positive"
+                else:
                     fidelity = (cur - new) / model
-                    margins.append(("fidelity", abs(float(fidelity) - MIN_FIDELITY), sensitivity))
+                    if np.isfinite(fidelity):  # an infinite current cost: no rounding path turns the test
+                        margins.append(("fidelity", abs(float(fidelity) - MIN_FIDELITY), sensitivity))
                     ok = bool(fidelity > MIN_FIDELITY)
+                    why = None if ok else "fidelity"
             if ok:
                 dec = cur - new
                 rel = dec / cur
@@ -323,12 +381,16 @@ def optimise(state: _State, k1, k2, uv1, uv2, opt, abs_tol=ABS_TOL, rel_tol=REL_
                 if trace is not None:
                     trace.append((float(cur), float(lam), float(dec)))
                 if dec < abs_tol or rel < rel_tol:
-                    stop = True
+                    stop, reason = True, "tolerance"
                 break
+            rejected[why] += 1
             lam = lam * dt(LAMBDA_FACTOR)
             if lam > LAMBDA_UPPER:
-                stop = True
+                stop, reason = True, "lambda_bound"
                 break
+    if report is not None:
+        report["stop"] = reason if stop else "step_limit"
+        report["rejected"] = rejected
     return state, first, cur, accepted, solves, margins
 
 
@@ -345,7 +407,8 @@ def two_view_ba(k1, k2, uv1, uv2, i2Ri1, i2Ui1, dtype=np.float64, order=None, se
     device reads them); ``i2Ri1`` [3, 3], ``i2Ui1`` [3]: the verifier's pose (NaN: none). ``order``: a permutation of the triangulated
     points applied before the optimisation (the first stays first), for the sensitivity measurement.
     Returns ``status``, ``rotation`` [3, 3] / ``translation`` [3] (NaN where the reference returns None), ``valid`` [n] bool,
-    ``points`` [n, 3] (NaN where not triangulated), ``cost`` (initial, final), ``stats`` [8], ``non_decisive``, ``triangulated`` [n] bool."""
+    ``points`` [n, 3] (NaN where not triangulated), ``cost`` (initial, final), ``stats`` [8], ``non_decisive``, ``triangulated`` [n] bool, and
+    for a pair that reaches the optimisation ``stop``, ``rejected`` and ``margins``."""
     unknown = set(options) - set(DEFAULTS)
     if unknown:
         raise TypeError(f"unknown options {sorted(unknown)}")
@@ -393,7 +456,7 @@ def two_view_ba(k1, k2, uv1, uv2, i2Ri1, i2Ui1, dtype=np.float64, order=None, se
     ka, kb, ua, ub = cast(k1), cast(k2), cast(uv1[idx]), cast(uv2[idx])
     state = _State(cast(np.eye(3)), cast(np.zeros(3)), cast(w_r1), cast(w_t1), cast(pts[idx]))
     p0 = state.pts[0].copy()
-    state, first, last, accepted, solves, margins = optimise(state, ka, kb, ua, ub, opt, abs_tol, rel_tol, trace, sensitivity)
+    state, first, last, accepted, solves, margins = optimise(state, ka, kb, ua, ub, opt, abs_tol, rel_tol, trace, sensitivity, report=out)
     out["cost"] = np.array([float(first), float(last)])
     out["stats"][4], out["stats"][5] = accepted, solves
     out["points"][idx] = state.pts.astype(np.float64)
@@ -401,12 +464,14 @@ def two_view_ba(k1, k2, uv1, uv2, i2Ri1, i2Ui1, dtype=np.float64, order=None, se
 
     # the undamped system at the final values
     v, w, gp, u, gc = linearise(state, ka, kb, ua, ub, p0, opt)
-    dc, _, ppiv, cpiv = schur_solve(v, w, gp, u, gc, dtype(0))
-    piv = np.concatenate([ppiv.reshape(-1), cpiv]).astype(np.float64)
-    scale = float(max(np.nanmax(np.abs(np.diagonal(u))), 1.0))
-    if np.isfinite(piv).any():
-        margins.append(("pivot", float(np.nanmin(np.abs(piv))), sensitivity * scale))
-    indeterminate = dc is None
+    _, _, ppiv, cpiv, why = schur_solve(v, w, gp, u, gc, dtype(0))
+    entry = pivot_margin(ppiv, cpiv, u, sensitivity, overflowed_points(state, ka, kb, ua, ub, opt))
+    if entry is not None:
+        margins.append(entry)
+    out["margins"] = margins
+    # the header's test: a PIVOT that is not positive or not finite. A solution that is not finite over pivots that are fine (a right-hand
+    # side that overflows) is not part of it, and the device, which factors without a right-hand side here, never sees one.
+    indeterminate = why in ("point_pivot", "camera_pivot")
     if indeterminate and not opt["allow_indeterminate"]:
         out["non_decisive"] = any(m <= band for _, m, band in margins)
         return done(INDETERMINATE)
@@ -424,7 +489,6 @@ def two_view_ba(k1, k2, uv1, uv2, i2Ri1, i2Ui1, dtype=np.float64, order=None, se
     out["rotation"] = r_rel.astype(np.float64)
     out["translation"] = (t_rel / np.sqrt(t_rel @ t_rel)).astype(np.float64)
     out["non_decisive"] = any(m <= band for _, m, band in margins)
-    out["margins"] = margins
     return done(INDETERMINATE if indeterminate else OK)
 
 

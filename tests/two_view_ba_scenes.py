@@ -182,3 +182,115 @@ def verified_scene_arrays(pairs: List[Dict[str, np.ndarray]], **layout_options) 
     return {"xy": xy, "launch": {"match_idx": lay["match_idx"], "match_off": lay["match_off"].tolist(), "match_count": counts, "mask": mask, "R": rot, "t": trans,
                                  "stats": stats, "pairs": [(2 * p, 2 * p + 1) for p in range(num)]},
             "putative": putative, "verified": verified, "intrinsics": lay["intrinsics"], "layout": lay}
+
+
+def make_general_pair(seed: int, n: int, rotvec=(0.0, -0.1, 0.0), centre=(1.0, 0.0, 0.0), focal: float = F, principal=(CX, CY), depth=(4.0, 9.0),
+                      planar: bool = False, translation_scale: float = 1.0, noise: float = 0.5, outliers: float = 0.1, perturb: float = 0.02) -> Dict[str, np.ndarray]:
+    """``make_pair`` with the geometry open: ``rotvec`` is the rotation vector of i2Ri1, camera 2's centre lies at ``centre`` (made unit:
+    the baseline is 1) in camera 1's frame, both cameras have the focal length ``focal`` (camera 2's 1 % longer) and the principal point
+    ``principal``; the points lie ``depth`` deep in front of camera 1 (``planar``: on one slanted plane through that range) and at least
+    0.5 deep in front of camera 2; the starting translation is the perturbed unit one times ``translation_scale``."""
+    rng = np.random.default_rng(seed)
+    r_true = _rot(np.asarray(rotvec, np.float64))
+    c = np.asarray(centre, np.float64) / np.linalg.norm(centre)
+    t_true = -r_true @ c
+    pts = np.zeros((0, 3))
+    while len(pts) < n:
+        cand = np.stack([rng.uniform(-2.0, 2.0, 4 * n), rng.uniform(-1.5, 1.5, 4 * n), rng.uniform(depth[0], depth[1], 4 * n)], axis=1)
+        if planar:
+            cand[:, 2] = 0.5 * (depth[0] + depth[1]) + 0.25 * (depth[1] - depth[0]) * (0.5 * cand[:, 0] + 0.3 * cand[:, 1])
+        pts = np.concatenate([pts, cand[(cand @ r_true.T + t_true)[:, 2] > 0.5]])
+    pts = pts[:n]
+    k1 = np.array([focal, focal, principal[0], principal[1]])
+    k2 = np.array([focal * 1.01, focal * 1.01, principal[0] + 3.0, principal[1] - 2.0])
+
+    def project(k, x):
+        return np.stack([k[0] * x[:, 0] / x[:, 2] + k[2], k[1] * x[:, 1] / x[:, 2] + k[3]], axis=1)
+
+    uv1 = project(k1, pts) + rng.normal(0.0, noise, (n, 2))
+    uv2 = project(k2, pts @ r_true.T + t_true) + rng.normal(0.0, noise, (n, 2))
+    bad = rng.random(n) < outliers
+    uv2[bad] += rng.normal(0.0, 2.5, (int(bad.sum()), 2))
+    r0 = _rot(rng.normal(0.0, perturb / np.sqrt(3.0), 3)) @ r_true
+    t0 = _rot(rng.normal(0.0, perturb / np.sqrt(3.0), 3)) @ t_true
+    return {"k1": k1, "k2": k2, "uv1": uv1.astype(np.float32), "uv2": uv2.astype(np.float32), "R": r0, "t": translation_scale * t0 / np.linalg.norm(t0),
+            "R_true": r_true, "t_true": t_true}
+
+
+def displaced_pair(seed: int, n: int, every: int = 3, by: float = 40.0, **kw) -> Dict[str, np.ndarray]:
+    """Every ``every``-th second pixel moved by ``by`` px in both coordinates: gross outliers that the Huber loss must carry."""
+    pair = make_pair(seed, n, **kw)
+    pair["uv2"][::every] += np.float32(by)
+    return pair
+
+
+def late_first_pair(seed: int, n: int = 300, late: int = 270) -> Dict[str, np.ndarray]:
+    """The first ``late`` correspondences cannot be triangulated (their second pixel is 400 px off: behind the cameras), so the first
+    triangulated one, which carries the point prior, is correspondence ``late``."""
+    pair = make_pair(seed, n)
+    pair["uv2"][:late, 0] += np.float32(400.0)
+    return pair
+
+
+HARD_FAMILIES = ("rejections", "step_limit", "late_first", "triangulation_options", "geometry", "loss", "strides", "non_finite", "non_decisive")
+DECISIVE_FAMILIES = HARD_FAMILIES[:-1]
+
+
+def hard_pairs() -> Dict[str, List[Dict[str, object]]]:
+    """The catalogue of hard pairs: family -> entries ``{"name", "pair", "options"}`` (``options``: what differs from the defaults of
+    tests/two_view_ba_reference.py). What every family must contain is asserted on the restatement by tests/test_two_view_ba_host.py; every
+    family but ``non_decisive`` holds decisive pairs only (the seeds were chosen for it)."""
+    def entry(name, pair, **options):
+        return {"name": name, "pair": pair, "options": options}
+
+    inf = float("inf")
+    out = {
+        # far starts and gross outliers: the fidelity test rejects trials, lambda climbs and comes back
+        "rejections": [entry("far_23", make_pair(23, 24, perturb=0.1)), entry("farther_506", make_pair(506, 24, perturb=0.2)),
+                       entry("farther_502", make_pair(502, 48, perturb=0.2)), entry("displaced_505", displaced_pair(505, 24)),
+                       entry("displaced_534", displaced_pair(534, 24)),
+                       entry("far_n300", make_pair(81, 300, perturb=0.1)), entry("far_n600", make_pair(81, 600, perturb=0.1))],
+        # the limit counts ACCEPTED steps: it cuts runs whose first solves were rejected, and a run with more than 100 solves at 100 steps
+        "step_limit": [entry(f"limit_{k}", make_pair(315, 24, perturb=0.1), max_iterations=k) for k in (1, 2, 3, 4)]  # left alone it stops by tolerance after 5 steps
+                      + [entry("behind_limit_5", behind_pair(), max_iterations=5), entry("displaced_100", displaced_pair(42, 24))],
+        # the point that carries the prior in a second stride (slice row >= 256), and in a lane other than 0 of the first
+        "late_first": [entry("second_stride_91", late_first_pair(91)), entry("second_stride_92", late_first_pair(92)),
+                       entry("other_lane", late_first_pair(91, n=150, late=100))],
+        "triangulation_options": [entry("threshold_2", make_pair(93, 40, outliers=0.3), triangulation_threshold=2.0),
+                                  entry("min_angle_1", make_pair(93, 40, outliers=0.3), triangulation_min_angle_deg=1.0),
+                                  # 20 - 120 deep at baseline 1: parallax 0.5 - 2.9 degrees, so one degree divides the points
+                                  entry("deep_min_angle_1", make_general_pair(602, 40, depth=(20.0, 120.0), outliers=0.3), triangulation_min_angle_deg=1.0),
+                                  entry("min_angle_8", make_pair(94, 40, outliers=0.3), triangulation_min_angle_deg=8.0)],
+        "geometry": [entry("planar", make_general_pair(61, 40, planar=True)), entry("wide_rotation", make_general_pair(62, 40, rotvec=(0.0, 0.9, 0.0))),
+                     entry("roll", make_general_pair(63, 40, rotvec=(0.0, 0.0, 3.1))),
+                     entry("long_focal", make_general_pair(64, 40, focal=3000.0, principal=(2000.0, 1500.0))),
+                     entry("translation_x5", make_general_pair(65, 40, translation_scale=5.0)),
+                     entry("translation_x1e-3", make_general_pair(95, 40, translation_scale=1e-3))],
+        "loss": [entry("no_robust_loss", make_pair(71, 40), huber_k=inf), entry("huber_0.1", make_pair(72, 40), huber_k=0.1),
+                 entry("sigma_0.5", make_pair(73, 40), measurement_sigma=0.5), entry("no_filter", make_pair(74, 40), reproj_error_threshold=inf)],
+        "strides": [entry("n1100", make_pair(99, 1100))],
+        # every scaled residual overflows: the initial cost is inf, every trial is rejected, lambda runs into its bound. The threshold of
+        # 4.2 px splits the entering points' reprojection errors (2.2 .. 5.9 px, none within 0.1 px of it): the filter's mask is neither
+        # empty nor full where the pair is let through, and empty only because the pair is given up where it is not
+        "non_finite": [entry("given_up", make_pair(400, 20, outliers=0.0), measurement_sigma=1e-160, reproj_error_threshold=4.2),
+                       entry("allowed", make_pair(400, 20, outliers=0.0), measurement_sigma=1e-160, reproj_error_threshold=4.2, allow_indeterminate=True)],
+        # honestly non-decisive: the undamped system's pivots are rounding-level by nature
+        "non_decisive": [entry("forward", make_general_pair(66, 40, centre=(0.05, 0.02, 1.0))),
+                         entry("translation_x1e3", make_general_pair(67, 40, translation_scale=1e3)), entry("rotation", rotation_pair())],
+    }
+    assert tuple(out) == HARD_FAMILIES
+    return out
+
+
+def dud_row_layouts(pair: Dict[str, np.ndarray], **layout_options):
+    """Three layouts of one pair that differ in one row below ``match_count``: (its mask at 0, the row verified with ``match_idx`` -1, the
+    row verified with a NaN pixel in its first keypoint), and the row. A verified row that cannot be triangulated counts as verified and
+    changes nothing else."""
+    base = capacity_layout([pair], **layout_options)
+    unverified = np.flatnonzero(base["inlier_mask"][:int(base["match_count"][0])] == 0)
+    row = int(unverified[len(unverified) // 2])
+    no_index, nan_pixel = ({k: np.array(v, copy=True) if isinstance(v, np.ndarray) else v for k, v in base.items()} for _ in range(2))
+    no_index["inlier_mask"][row] = nan_pixel["inlier_mask"][row] = 1
+    no_index["match_idx"][row] = -1
+    nan_pixel["kp_xy"][int(base["kp_off1"][0]) + int(base["match_idx"][row, 0]), 0] = np.nan
+    return base, no_index, nan_pixel, row

@@ -4,7 +4,11 @@
 //
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off [-Xarch_host -fsanitize=address,undefined] -c tools/two_view_ba_host_main.cpp -o main.o
 //   hipcc [-fsanitize=address,undefined] main.o -o two_view_ba_host
-//   two_view_ba_host scene.bin out.bin
+//   two_view_ba_host scene.bin out.bin [trace.txt]
+//
+// trace.txt (optional): one line per rejected trial of the second run, "pair solve lambda route" -- route: poisoned (a point block without a
+// positive pivot, or a sum that is NaN, before the solve), camera_solve (the 12 x 12 factorisation or its solution), cost_not_finite,
+// model_not_positive, fidelity -- and one line "pair stop tolerance | lambda_bound | step_limit" per pair that reaches the loop.
 //
 // scene.bin: int64 {magic, P, M, keypoint rows, max_iterations, min_verified, allow_indeterminate, 1 with match_count}, double {reproj
 // threshold, huber_k, measurement / pose prior / point prior sigma, triangulation threshold, triangulation min angle, 0}, float
@@ -134,7 +138,7 @@ void block_sum(const std::vector<double>& lane, int n, double* out) {
 }
 
 // the adjust kernel's workgroup for pair p, by one lane or by the device's partition
-void adjust_pair(const Scene& s, const TvbaWorkspace& w, int p, bool device_partition, Outputs& out) {
+void adjust_pair(const Scene& s, const TvbaWorkspace& w, int p, bool device_partition, Outputs& out, FILE* trace) {
     const TvbaOptions opt = {s.huber_k, 1.0 / s.sigma, 1.0 / s.pose_sigma, 1.0 / (s.point_sigma * s.point_sigma)};
     long long a, count;
     bool bad;
@@ -255,6 +259,7 @@ void adjust_pair(const Scene& s, const TvbaWorkspace& w, int p, bool device_part
     while (ctl.accepted < s.max_iterations && !ctl.stop) {
         const double lam = ctl.lam;
         reduced_system(lam);
+        const bool poisoned = sum[0] != sum[0];
         tvba_solve_trial(ctl, sum, opt.pose_prior_inv_sigma, pose, trial_pose, low, rhs, dc);
         double gtd = 0.0, dd = 0.0, fresh = NAN;
         if (ctl.solved) {
@@ -269,7 +274,13 @@ void adjust_pair(const Scene& s, const TvbaWorkspace& w, int p, bool device_part
         }
         tvba_decide(ctl, gtd, dd, fresh, pose, trial_pose);
         if (ctl.accept) accept_points();
+        if (trace && !ctl.accept) {
+            const double model = -0.5 * gtd + 0.5 * lam * dd;
+            const char* route = poisoned ? "poisoned" : !ctl.solved ? "camera_solve" : !isfinite(fresh) ? "cost_not_finite" : !(model > 0.0) ? "model_not_positive" : "fidelity";
+            fprintf(trace, "%d %d %.17g %s\n", p, ctl.solves, lam, route);
+        }
     }
+    if (trace) fprintf(trace, "%d stop %s\n", p, !ctl.stop ? "step_limit" : ctl.accept ? "tolerance" : "lambda_bound");
     reduced_system(0.0);
     tvba_pose_prior(pose[0], opt.pose_prior_inv_sigma, sum);
     const bool indeterminate = !tvba_cholesky12(sum, 0.0, nullptr, low, nullptr);
@@ -293,7 +304,7 @@ void adjust_pair(const Scene& s, const TvbaWorkspace& w, int p, bool device_part
 }
 
 // 0, or the error flag's exit status
-int run(const Scene& s, bool second, Outputs& out) {
+int run(const Scene& s, bool second, Outputs& out, FILE* trace) {
     const size_t bytes = tvba_layout(nullptr, s.num_pairs, s.total).bytes;
     void* base = aligned_alloc(256, bytes);
     if (!base) return 1;
@@ -315,7 +326,7 @@ int run(const Scene& s, bool second, Outputs& out) {
             tri_final_track(j, w.track_off, w.image, w.uv, s.total, w.cams, 2 * (int)s.num_pairs, TRI_NO_RANSAC, s.tri_threshold, s.tri_angle, t.hyp_off, t.hyp, t.cap,
                             t.flags, w.tri_point, w.tri_avg, w.tri_exit, w.tri_mask, w.tri_stats);
     }
-    for (int p = 0; p < (int)s.num_pairs; ++p) adjust_pair(s, w, p, second, out);
+    for (int p = 0; p < (int)s.num_pairs; ++p) adjust_pair(s, w, p, second, out, trace);
     const int status = w.flags[0] ? 3 : 0;
     free(base);
     return status;
@@ -324,8 +335,8 @@ int run(const Scene& s, bool second, Outputs& out) {
 }  // namespace
 
 int main(int argc, char** argv) {
-    if (argc != 3) {
-        fprintf(stderr, "usage: %s scene.bin out.bin\n", argv[0]);
+    if (argc != 3 && argc != 4) {
+        fprintf(stderr, "usage: %s scene.bin out.bin [trace.txt]\n", argv[0]);
         return 1;
     }
     Scene s;
@@ -339,8 +350,14 @@ int main(int argc, char** argv) {
         return 1;
     }
     Outputs first(s, 0x00), second(s, 0xFF);
-    int status = run(s, false, first);
-    const int other = run(s, true, second);
+    FILE* trace = argc == 4 ? fopen(argv[3], "w") : nullptr;
+    if (argc == 4 && !trace) {
+        fprintf(stderr, "%s: cannot write\n", argv[3]);
+        return 1;
+    }
+    int status = run(s, false, first, nullptr);
+    const int other = run(s, true, second, trace);
+    if (trace) fclose(trace);
     if (status != other) status = 2;
     if (status == 0 && !first.same(second)) {
         fprintf(stderr, "the outputs depend on the order of the lanes or on what the memory held\n");
