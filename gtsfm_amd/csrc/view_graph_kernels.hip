@@ -1,0 +1,694 @@
+// View-graph estimation on the device: the rotation cycle-consistency filter and the largest connected component. See include/gtsfm_amd.h.
+//
+// A vertex is an image, an edge is a row (i1, i2, i2Ri1) of the two-view stage's arrays. Everything but the cycle angle is integer work,
+// and every output byte is fixed by the SET of input edges and their rotations: not by the order of the rows, the grid, or timing.
+//
+// ADJACENCY: CSR with per-vertex sorted neighbour lists, each entry carrying the row of its edge. An N x N bit matrix would find the common
+// neighbours of (a, b) by AND / popcount, but the cycle error needs the ROWS of (a, c) and (b, c) to fetch their rotations, which a bit does
+// not give, and its size grows with the square of the image count where the pair graph of a scene is sparse (a retrieval window): CSR is
+// 8 bytes per list entry whatever num_images is, and a merge of two sorted lists yields both rows of every common neighbour.
+//   degree : per enabled edge, atomicAdd on both endpoints' degree (integer adds, any order); the edge's input flag (nine finite numbers).
+//   scan   : exclusive prefix sum of the degrees (one workgroup).
+//   fill   : an edge takes slot row_off[v] + atomicAdd(&cursor[v], 1) in both lists: arbitrary order, in bounds since exactly degree ask.
+//   rank   : per list entry, over its vertex's list: rank = entries with a smaller (neighbour, row); the entry moves to that place of the
+//            sorted list. Another entry with the same neighbour is a duplicate edge and raises a flag. Lists are short (the degree), so
+//            this costs the sum of squared degrees and needs no sort.
+//   The host reads the two flags (bad pair, duplicate) here, before any output is written.
+//
+// TRIPLETS. The slot of edge (a, b), a < b, in a's sorted list is its place in the lexicographic order of all edges. Per such slot:
+//   count  : merge the lists of a and b; a common neighbour c whose two edges are input edges is a triplet. All of them, and those with
+//            c > b (the triplet's lexicographically first edge owns it: each distinct triplet once, in lexicographic order).
+//   scan   : both counts over the slots; the host reads the two totals (the second and last readback) and checks the capacities.
+//   fill   : the same merge; the j-th common neighbour's cycle error goes to the edge's own segment, so the segment's order is that of c.
+//            Each edge evaluates its triplets itself, on the SORTED triplet by one instruction sequence (vg_cycle_error_deg), so the three
+//            edges of a triplet hold the same bytes and nothing is scattered.
+//   aggregate : one wave per edge row; a lane takes the elements lane, lane + 64, ... of the segment and ranks each against the whole
+//            segment by (value, index). The lane holding rank (n - 1) / 2 (or 0 for MIN) also finds its successor's value and writes the
+//            aggregate: any count is handled by the same loop, no lane or wave capacity exists. A NaN in the segment gives NaN (numpy's
+//            min and median) and the edge is dropped.
+//
+// COMPONENTS (gtsfm_largest_component): the hook / compress rounds of tracks_kernels.hip over the images, with the same invariants
+// (parent[x] <= x, labels only decrease, no kernel waits for another workgroup, the host reads a 4-byte flag per round and refuses after
+// 64). Then the size of every component at its root; the winner is the largest, of equally large ones the owner of the smallest enabled row.
+// COUNTS are taken by one workgroup that walks the rows, not by atomics on one word.
+//
+// Every per-index step is a VG_HD function that the kernels call with their global index and tools/view_graph_host_main.cpp calls in
+// another order on a CPU; the atomics become plain updates there.
+
+#include <math.h>
+
+#include "../../include/gtsfm_amd.h"
+#include "common.h"
+
+#define VG_HD __host__ __device__ __forceinline__
+#define VG_THREADS 256
+#define VG_WAVE 64
+#define VG_SCAN_THREADS 1024
+#define VG_SCAN_ITEMS 4
+#define VG_SCAN_BLOCK (VG_SCAN_THREADS * VG_SCAN_ITEMS)
+#define VG_MAX_ROUNDS 64
+#define VG_FLAG_WORDS (8 + VG_MAX_ROUNDS)  // word 0: a bad pair; word 1: a duplicate edge; word 8 + r: round r hooked something
+#define VG_MAX_EDGES (1ll << 28)
+#define VG_MAX_IMAGES (1ll << 28)
+#define VG_MAX_TRIPLETS ((1ll << 31) / 3)
+#define VG_RAD_TO_DEG 57.29577951308232  // 180 / pi, numpy's rad2deg factor
+
+typedef unsigned long long vg_u64;
+
+namespace {
+
+VG_HD int vg_atomic_add(int* p, int v) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return atomicAdd(p, v);
+#else
+    const int old = *p;
+    *p = old + v;
+    return old;
+#endif
+}
+VG_HD long long vg_atomic_add64(long long* p, long long v) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return (long long)atomicAdd((vg_u64*)p, (vg_u64)v);
+#else
+    const long long old = *p;
+    *p = old + v;
+    return old;
+#endif
+}
+VG_HD void vg_atomic_min(int* p, int v) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    atomicMin(p, v);
+#else
+    if (v < *p) *p = v;
+#endif
+}
+
+// ---- the cycle error ----
+
+// The angle in degrees of M = i2Ri0^T . i2Ri1 . i1Ri0 (products in that order, sums left to right), the way scipy's
+// Rotation.from_matrix(M).as_rotvec() norm finds it: the quaternion from the largest of the diagonal and the trace (the first largest),
+// normalised, then 2 atan2(|q_xyz|, |q_w|).
+VG_HD double vg_cycle_error_deg(const double* __restrict__ i1Ri0, const double* __restrict__ i2Ri1, const double* __restrict__ i2Ri0) {
+    double a[9], m[9];
+    for (int r = 0; r < 3; ++r)
+        for (int c = 0; c < 3; ++c) a[3 * r + c] = i2Ri0[r] * i2Ri1[c] + i2Ri0[3 + r] * i2Ri1[3 + c] + i2Ri0[6 + r] * i2Ri1[6 + c];
+    for (int r = 0; r < 3; ++r)
+        for (int c = 0; c < 3; ++c) m[3 * r + c] = a[3 * r] * i1Ri0[c] + a[3 * r + 1] * i1Ri0[3 + c] + a[3 * r + 2] * i1Ri0[6 + c];
+    const double trace = m[0] + m[4] + m[8];
+    int choice = 0;
+    double best = m[0];
+    if (m[4] > best) best = m[4], choice = 1;
+    if (m[8] > best) best = m[8], choice = 2;
+    if (trace > best) choice = 3;
+    double qx, qy, qz, qw;  // scipy's (i, j, k) = (choice, choice + 1, choice + 2) mod 3, written out: no indexed registers
+    if (choice == 0) {
+        qx = 1 - trace + 2 * m[0], qy = m[3] + m[1], qz = m[6] + m[2], qw = m[7] - m[5];
+    } else if (choice == 1) {
+        qy = 1 - trace + 2 * m[4], qz = m[7] + m[5], qx = m[1] + m[3], qw = m[2] - m[6];
+    } else if (choice == 2) {
+        qz = 1 - trace + 2 * m[8], qx = m[2] + m[6], qy = m[5] + m[7], qw = m[3] - m[1];
+    } else {
+        qx = m[7] - m[5], qy = m[2] - m[6], qz = m[3] - m[1], qw = 1 + trace;
+    }
+    const double norm = sqrt(qx * qx + qy * qy + qz * qz + qw * qw);
+    qx /= norm, qy /= norm, qz /= norm, qw /= norm;
+    const double angle = 2 * atan2(sqrt(qx * qx + qy * qy + qz * qz), fabs(qw));
+    return angle * VG_RAD_TO_DEG;
+}
+
+// ---- the cycle filter ----
+
+struct VgWorkspace {
+    long long *row_off, *seg_off, *trip_off;  // [N + 1] degrees then list offsets; [2 E + 1] per slot: triplets, those it owns, then offsets
+    int *cursor, *raw_nbr, *raw_edge, *adj_nbr, *adj_edge, *slot_of_edge, *flags;
+    uint8_t* input;
+    double* errs;  // [3 triplet_capacity] the per-edge error lists
+    size_t fixed_bytes, bytes;
+};
+
+VgWorkspace vg_layout(void* base, long long num_edges, long long num_images, long long triplet_capacity) {
+    VgWorkspace w;
+    size_t used = 0;
+    const size_t e = (size_t)num_edges, n = (size_t)num_images;
+    auto take = [&](size_t bytes) {
+        const size_t at = used;
+        used += align_up(bytes, 256);
+        return (void*)((uintptr_t)base + at);
+    };
+    w.row_off = (long long*)take((n + 1) * 8);
+    w.seg_off = (long long*)take((2 * e + 1) * 8);
+    w.trip_off = (long long*)take((2 * e + 1) * 8);
+    w.cursor = (int*)take(n * 4);
+    w.raw_nbr = (int*)take(2 * e * 4);
+    w.raw_edge = (int*)take(2 * e * 4);
+    w.adj_nbr = (int*)take(2 * e * 4);
+    w.adj_edge = (int*)take(2 * e * 4);
+    w.slot_of_edge = (int*)take(e * 4);
+    w.flags = (int*)take(VG_FLAG_WORDS * 4);
+    w.input = (uint8_t*)take(e);
+    w.fixed_bytes = used;
+    w.errs = (double*)take(3 * (size_t)triplet_capacity * 8);
+    w.bytes = used;
+    return w;
+}
+
+struct VgGraph {  // what the per-index functions of the filter read and write
+    const int* pair_images;
+    const double* rotation;
+    const uint8_t* pair_enable;
+    long long num_edges;
+    int num_images;
+    VgWorkspace w;
+};
+
+// an enabled row whose pair is in order and in range; every kernel tests it again, so a bad row is never followed anywhere
+VG_HD bool vg_edge_usable(const VgGraph& g, long long e, int* i1, int* i2) {
+    if (g.pair_enable && !g.pair_enable[e]) return false;
+    *i1 = g.pair_images[2 * e];
+    *i2 = g.pair_images[2 * e + 1];
+    return *i1 >= 0 && *i1 < *i2 && *i2 < g.num_images;
+}
+
+VG_HD void vg_init(const VgGraph& g, long long i) {
+    if (i < VG_FLAG_WORDS) g.w.flags[i] = 0;
+    if (i <= g.num_images) g.w.row_off[i] = 0;
+    if (i < g.num_images) g.w.cursor[i] = 0;
+}
+
+VG_HD void vg_edge_degree(const VgGraph& g, long long e) {
+    int i1, i2;
+    g.w.input[e] = 0;
+    if (!vg_edge_usable(g, e, &i1, &i2)) {
+        if (!g.pair_enable || g.pair_enable[e]) g.w.flags[0] = 1;
+        return;
+    }
+    vg_atomic_add64(&g.w.row_off[i1], 1);
+    vg_atomic_add64(&g.w.row_off[i2], 1);
+    bool finite = true;
+    for (int k = 0; k < 9; ++k) finite = finite && isfinite(g.rotation[9 * e + k]);
+    g.w.input[e] = finite ? 1 : 0;
+}
+
+VG_HD void vg_edge_fill(const VgGraph& g, long long e) {
+    int i1, i2;
+    if (!vg_edge_usable(g, e, &i1, &i2)) return;
+    const long long s1 = g.w.row_off[i1] + vg_atomic_add(&g.w.cursor[i1], 1), s2 = g.w.row_off[i2] + vg_atomic_add(&g.w.cursor[i2], 1);
+    if (s1 < g.w.row_off[i1 + 1]) g.w.raw_nbr[s1] = i2, g.w.raw_edge[s1] = (int)e;  // always true: exactly degree rows ask
+    if (s2 < g.w.row_off[i2 + 1]) g.w.raw_nbr[s2] = i1, g.w.raw_edge[s2] = (int)e;
+}
+
+// the vertex whose list holds an entry (neighbour, row): the row's other endpoint
+VG_HD int vg_owner(const VgGraph& g, int nbr, int edge) {
+    const int i1 = g.pair_images[2 * (long long)edge], i2 = g.pair_images[2 * (long long)edge + 1];
+    return i1 == nbr ? i2 : i1;
+}
+
+VG_HD void vg_slot_rank(const VgGraph& g, long long s) {
+    if (s >= g.w.row_off[g.num_images]) return;
+    const int nbr = g.w.raw_nbr[s], edge = g.w.raw_edge[s], owner = vg_owner(g, nbr, edge);
+    const long long lo = g.w.row_off[owner], hi = g.w.row_off[owner + 1];
+    long long rank = 0;
+    for (long long j = lo; j < hi; ++j) {
+        const int nj = g.w.raw_nbr[j], ej = g.w.raw_edge[j];
+        if (nj < nbr || (nj == nbr && ej < edge)) ++rank;
+        if (nj == nbr && ej != edge) g.w.flags[1] = 1;
+    }
+    g.w.adj_nbr[lo + rank] = nbr;
+    g.w.adj_edge[lo + rank] = edge;
+    if (owner < nbr) g.w.slot_of_edge[edge] = (int)(lo + rank);
+}
+
+// The triplets of sorted slot s = edge (a, b) with a < b, by a merge of the two sorted lists. fill == false: seg_off[s] / trip_off[s]
+// receive the counts (all, and those with c > b). fill == true (after the scans): the errors go to the edge's segment, and the triplets
+// this edge owns to the triplet list.
+VG_HD void vg_slot_triplets(const VgGraph& g, long long s, bool fill, int* __restrict__ triplets, double* __restrict__ cycle_error) {
+    long long all = 0, own = 0;
+    if (s < g.w.row_off[g.num_images]) {
+        const int b = g.w.adj_nbr[s], e = g.w.adj_edge[s], a = vg_owner(g, b, e);
+        if (a < b && g.w.input[e]) {
+            long long pa = g.w.row_off[a], pb = g.w.row_off[b];
+            const long long ea = g.w.row_off[a + 1], eb = g.w.row_off[b + 1];
+            const long long seg = fill ? g.w.seg_off[s] : 0, trip = fill ? g.w.trip_off[s] : 0;
+            while (pa < ea && pb < eb) {
+                const int ca = g.w.adj_nbr[pa], cb = g.w.adj_nbr[pb];
+                if (ca < cb) {
+                    ++pa;
+                } else if (cb < ca) {
+                    ++pb;
+                } else {
+                    const int eac = g.w.adj_edge[pa], ebc = g.w.adj_edge[pb];
+                    if (g.w.input[eac] && g.w.input[ebc]) {
+                        const int c = ca;
+                        if (fill) {
+                            const double *rab = g.rotation + 9 * (long long)e, *rac = g.rotation + 9 * (long long)eac, *rbc = g.rotation + 9 * (long long)ebc;
+                            // (i1Ri0, i2Ri1, i2Ri0) of the sorted triplet
+                            const double err = c < a ? vg_cycle_error_deg(rac, rab, rbc) : (c < b ? vg_cycle_error_deg(rac, rbc, rab) : vg_cycle_error_deg(rab, rbc, rac));
+                            g.w.errs[seg + all] = err;
+                            if (c > b && triplets) {
+                                triplets[3 * (trip + own)] = a, triplets[3 * (trip + own) + 1] = b, triplets[3 * (trip + own) + 2] = c;
+                                cycle_error[trip + own] = err;
+                            }
+                        }
+                        ++all;
+                        if (c > b) ++own;
+                    }
+                    ++pa, ++pb;
+                }
+            }
+        }
+    }
+    if (!fill) g.w.seg_off[s] = all, g.w.trip_off[s] = own;
+}
+
+// Lane `lane` of `lanes` for edge row e: see the header comment.
+VG_HD void vg_edge_aggregate(const VgGraph& g, long long e, int lane, int lanes, int criterion, double threshold, int* __restrict__ num_triplets,
+                             double* __restrict__ aggregate, uint8_t* __restrict__ keep) {
+    const double nan = __builtin_nan("");
+    if (!g.w.input[e]) {
+        if (lane == 0) num_triplets[e] = 0, aggregate[e] = nan, keep[e] = 0;
+        return;
+    }
+    const long long s = g.w.slot_of_edge[e], base = g.w.seg_off[s], n = g.w.seg_off[s + 1] - base;
+    if (n == 0) {
+        if (lane == 0) num_triplets[e] = 0, aggregate[e] = nan, keep[e] = 1;
+        return;
+    }
+    const bool median = criterion == 1;
+    const long long k = median ? (n - 1) / 2 : 0;
+    const bool two = median && n % 2 == 0;
+    const double* x = g.w.errs + base;
+    for (long long j = lane; j < n; j += lanes) {
+        const double xj = x[j];
+        long long rank = 0;
+        bool has_nan = false;
+        double succ = HUGE_VAL;
+        for (long long i = 0; i < n; ++i) {
+            const double xi = x[i];
+            has_nan = has_nan || xi != xi;
+            if (xi < xj || (xi == xj && i < j)) ++rank;
+            if ((xi > xj || (xi == xj && i > j)) && xi < succ) succ = xi;
+        }
+        if (has_nan ? j != 0 : rank != k) continue;
+        const double value = has_nan ? nan : (two ? (xj + succ) / 2 : xj);
+        const bool kept = value < threshold;
+        num_triplets[e] = (int)n, aggregate[e] = value, keep[e] = kept ? 1 : 0;
+    }
+}
+
+// ---- the largest component ----
+
+struct VgComponents {
+    const int* pair_images;
+    const uint8_t* pair_enable;
+    long long num_edges;
+    int num_images;
+    int *parent, *label, *mark, *cnt, *flags;
+    vg_u64* best;  // (size << 32) | (INT_MAX - smallest enabled row) of the winning component; 0: no enabled edge
+    size_t bytes;
+};
+
+VgComponents vg_cc_layout(void* base, long long num_images) {
+    VgComponents w;
+    size_t used = 0;
+    const size_t n = (size_t)num_images;
+    auto take = [&](size_t bytes) {
+        const size_t at = used;
+        used += align_up(bytes, 256);
+        return (void*)((uintptr_t)base + at);
+    };
+    w.parent = (int*)take(n * 4);
+    w.label = (int*)take(n * 4);
+    w.mark = (int*)take(n * 4);
+    w.cnt = (int*)take(n * 4);
+    w.flags = (int*)take(VG_FLAG_WORDS * 4);
+    w.best = (vg_u64*)take(8);
+    w.bytes = used;
+    return w;
+}
+
+VG_HD bool vg_cc_edge(const VgComponents& g, long long e, int* i1, int* i2) {
+    if (g.pair_enable && !g.pair_enable[e]) return false;
+    *i1 = g.pair_images[2 * e];
+    *i2 = g.pair_images[2 * e + 1];
+    return *i1 >= 0 && *i1 < g.num_images && *i2 >= 0 && *i2 < g.num_images;
+}
+
+VG_HD void vg_cc_init(const VgComponents& g, long long v) {
+    if (v < VG_FLAG_WORDS) g.flags[v] = 0;
+    if (v == 0) *g.best = 0;
+    if (v >= g.num_images) return;
+    g.parent[v] = g.label[v] = (int)v;
+    g.mark[v] = g.cnt[v] = 0;
+}
+
+VG_HD void vg_cc_hook(const VgComponents& g, long long e, int round) {
+    int u, v;
+    if (!vg_cc_edge(g, e, &u, &v)) {
+        if (!g.pair_enable || g.pair_enable[e]) g.flags[0] = 1;
+        return;
+    }
+    if (round == 0) g.mark[u] = 1, g.mark[v] = 1;
+    const int ru = g.label[u], rv = g.label[v];
+    if (ru != rv) {
+        vg_atomic_min(&g.parent[ru > rv ? ru : rv], ru < rv ? ru : rv);
+        g.flags[8 + round] = 1;
+    }
+}
+
+VG_HD void vg_cc_compress(const VgComponents& g, long long v) {
+    int x = g.parent[v];
+    for (int p = g.parent[x]; p != x; p = g.parent[x]) x = p;  // strictly decreasing: parent[x] <= x
+    g.label[v] = x;
+    g.parent[v] = x;
+}
+
+VG_HD void vg_cc_node_count(const VgComponents& g, long long v) {
+    if (g.mark[v]) vg_atomic_add(&g.cnt[g.label[v]], 1);
+}
+
+// The winner is the largest component, and of equally large ones the one that owns the first edge listed: an enabled row bids when its
+// component has the largest size, INT_MAX - row, and the largest bid wins. (A per-root minimum row by atomicMin would put every edge of a
+// connected scene on one word: measured 0.5 ms at 43 867 edges.)
+VG_HD vg_u64 vg_cc_edge_bid(const VgComponents& g, long long e, int largest) {
+    int u, v;
+    return vg_cc_edge(g, e, &u, &v) && g.cnt[g.label[u]] == largest ? (vg_u64)(0x7FFFFFFF - e) : 0;
+}
+
+// the winner's label, or -1 without an enabled edge
+VG_HD int vg_cc_root_of_key(const VgComponents& g, vg_u64 best) {
+    if (best == 0) return -1;
+    const long long row = 0x7FFFFFFF - (long long)(unsigned)(best & 0xFFFFFFFFull);
+    return g.label[g.pair_images[2 * row]];
+}
+
+VG_HD bool vg_cc_edge_kept(const VgComponents& g, long long e, int root) {
+    int u, v;
+    return root >= 0 && vg_cc_edge(g, e, &u, &v) && g.label[u] == root;
+}
+
+VG_HD void vg_cc_write_node(const VgComponents& g, long long v, uint8_t* __restrict__ node_mask) {
+    const int root = vg_cc_root_of_key(g, *g.best);
+    node_mask[v] = (root >= 0 && g.mark[v] && g.label[v] == root) ? 1 : 0;
+}
+
+VG_HD void vg_cc_write_edge(const VgComponents& g, long long e, uint8_t* __restrict__ pair_keep) {
+    pair_keep[e] = vg_cc_edge_kept(g, e, vg_cc_root_of_key(g, *g.best)) ? 1 : 0;
+}
+
+// ---- kernels: one index per thread (one wave per edge for the aggregate) ----
+
+#define VG_INDEX const long long i = (long long)blockIdx.x * VG_THREADS + threadIdx.x
+
+__global__ __launch_bounds__(VG_THREADS) void vg_init_kernel(VgGraph g, long long n) {
+    VG_INDEX;
+    if (i < n) vg_init(g, i);
+}
+__global__ __launch_bounds__(VG_THREADS) void vg_edge_degree_kernel(VgGraph g) {
+    VG_INDEX;
+    if (i < g.num_edges) vg_edge_degree(g, i);
+}
+__global__ __launch_bounds__(VG_THREADS) void vg_edge_fill_kernel(VgGraph g) {
+    VG_INDEX;
+    if (i < g.num_edges) vg_edge_fill(g, i);
+}
+__global__ __launch_bounds__(VG_THREADS) void vg_slot_rank_kernel(VgGraph g) {
+    VG_INDEX;
+    if (i < 2 * g.num_edges) vg_slot_rank(g, i);
+}
+__global__ __launch_bounds__(VG_THREADS) void vg_slot_triplets_kernel(VgGraph g, int fill, int* __restrict__ triplets, double* __restrict__ cycle_error) {
+    VG_INDEX;
+    if (i < 2 * g.num_edges) vg_slot_triplets(g, i, fill != 0, triplets, cycle_error);
+}
+__global__ __launch_bounds__(VG_THREADS) void vg_edge_aggregate_kernel(VgGraph g, int criterion, double threshold,
+                                                                        int* __restrict__ num_triplets, double* __restrict__ aggregate,
+                                                                        uint8_t* __restrict__ keep) {
+    const long long e = (long long)blockIdx.x * (VG_THREADS / VG_WAVE) + threadIdx.x / VG_WAVE;
+    if (e < g.num_edges) vg_edge_aggregate(g, e, threadIdx.x % VG_WAVE, VG_WAVE, criterion, threshold, num_triplets, aggregate, keep);
+}
+
+__global__ __launch_bounds__(VG_THREADS) void vg_cc_init_kernel(VgComponents g, long long n) {
+    VG_INDEX;
+    if (i < n) vg_cc_init(g, i);
+}
+__global__ __launch_bounds__(VG_THREADS) void vg_cc_hook_kernel(VgComponents g, int round) {
+    VG_INDEX;
+    if (i < g.num_edges) vg_cc_hook(g, i, round);
+}
+__global__ __launch_bounds__(VG_THREADS) void vg_cc_compress_kernel(VgComponents g) {
+    VG_INDEX;
+    if (i < g.num_images) vg_cc_compress(g, i);
+}
+__global__ __launch_bounds__(VG_THREADS) void vg_cc_node_count_kernel(VgComponents g) {
+    VG_INDEX;
+    if (i < g.num_images) vg_cc_node_count(g, i);
+}
+__global__ __launch_bounds__(VG_THREADS) void vg_cc_write_node_kernel(VgComponents g, uint8_t* __restrict__ node_mask) {
+    VG_INDEX;
+    if (i < g.num_images) vg_cc_write_node(g, i, node_mask);
+}
+__global__ __launch_bounds__(VG_THREADS) void vg_cc_write_edge_kernel(VgComponents g, uint8_t* __restrict__ pair_keep) {
+    VG_INDEX;
+    if (i < g.num_edges) vg_cc_write_edge(g, i, pair_keep);
+}
+
+// ---- the counts: ONE workgroup walks the rows and combines by a tree. Tens of thousands of atomics on one word would serialise (measured:
+// 11 ns each, 1.6 ms of the aggregate kernel's 1.65 ms at 48 725 edges); a walk of the same rows by 1024 lanes does not.
+
+template <class T, class Op>
+__device__ __forceinline__ T vg_block_reduce(T x, T* lds /*[VG_SCAN_THREADS]*/, Op op) {
+    const int tid = threadIdx.x;
+    lds[tid] = x;
+    __syncthreads();
+    for (int off = VG_SCAN_THREADS / 2; off > 0; off >>= 1) {
+        if (tid < off) lds[tid] = op(lds[tid], lds[tid + off]);
+        __syncthreads();
+    }
+    const T all = lds[0];
+    __syncthreads();  // lds may be reused
+    return all;
+}
+
+__global__ __launch_bounds__(VG_SCAN_THREADS) void vg_filter_counts_kernel(const uint8_t* __restrict__ input, const uint8_t* __restrict__ keep,
+                                                                          const int* __restrict__ num_triplets, long long num_edges, long long total_triplets,
+                                                                          int* __restrict__ counts) {
+    __shared__ long long lds[VG_SCAN_THREADS];
+    long long in = 0, kept = 0, most = 0;
+    for (long long e = threadIdx.x; e < num_edges; e += VG_SCAN_THREADS) {
+        in += input[e] ? 1 : 0;
+        kept += keep[e] ? 1 : 0;
+        most = num_triplets[e] > most ? num_triplets[e] : most;
+    }
+    const auto add = [](long long a, long long b) { return a + b; };
+    in = vg_block_reduce(in, lds, add);
+    kept = vg_block_reduce(kept, lds, add);
+    most = vg_block_reduce(most, lds, [](long long a, long long b) { return a > b ? a : b; });
+    if (threadIdx.x == 0) {
+        counts[0] = (int)in, counts[1] = (int)kept, counts[2] = (int)total_triplets, counts[3] = (int)most;
+        counts[4] = counts[5] = counts[6] = counts[7] = 0;
+    }
+}
+
+// the largest size and the roots over the nodes, the winning bid over the rows (stored with the size in *g.best for the two write
+// kernels), then the component's edges
+__global__ __launch_bounds__(VG_SCAN_THREADS) void vg_cc_summary_kernel(VgComponents g, int* __restrict__ counts) {
+    __shared__ vg_u64 lds[VG_SCAN_THREADS];
+    vg_u64 largest = 0, components = 0, bid = 0, edges = 0;
+    for (long long v = threadIdx.x; v < g.num_images; v += VG_SCAN_THREADS) {
+        const vg_u64 size = g.cnt[v] > 0 ? (vg_u64)g.cnt[v] : 0;  // cnt is nonzero at the roots of components with an edge only
+        components += size ? 1 : 0;
+        largest = size > largest ? size : largest;
+    }
+    const auto add = [](vg_u64 a, vg_u64 b) { return a + b; };
+    const auto most = [](vg_u64 a, vg_u64 b) { return a > b ? a : b; };
+    largest = vg_block_reduce(largest, lds, most);
+    components = vg_block_reduce(components, lds, add);
+    for (long long e = threadIdx.x; e < g.num_edges && largest; e += VG_SCAN_THREADS) {
+        const vg_u64 b = vg_cc_edge_bid(g, e, (int)largest);
+        bid = b > bid ? b : bid;
+    }
+    bid = vg_block_reduce(bid, lds, most);
+    const vg_u64 best = largest ? (largest << 32) | bid : 0;
+    const int root = vg_cc_root_of_key(g, best);
+    for (long long e = threadIdx.x; e < g.num_edges; e += VG_SCAN_THREADS) edges += vg_cc_edge_kept(g, e, root) ? 1 : 0;
+    edges = vg_block_reduce(edges, lds, add);
+    if (threadIdx.x == 0) {
+        *g.best = best;
+        counts[0] = (int)(best >> 32), counts[1] = (int)edges, counts[2] = (int)components;
+        counts[3] = counts[4] = counts[5] = counts[6] = counts[7] = 0;
+    }
+}
+
+// val[0 .. n) -> its exclusive prefix sum in place, val[n] = the total. One workgroup walks the array in blocks of VG_SCAN_BLOCK: the
+// arrays here are a few hundred thousand entries at most, and a single launch keeps the carry in a register.
+__global__ __launch_bounds__(VG_SCAN_THREADS) void vg_scan_kernel(long long* val, long long n) {
+    __shared__ long long lds[VG_SCAN_THREADS];
+    const int tid = threadIdx.x;
+    long long carry = 0;
+    for (long long base = 0; base < n; base += VG_SCAN_BLOCK) {  // n and base are uniform: the barriers stay matched
+        const long long at = base + (long long)tid * VG_SCAN_ITEMS;
+        long long x[VG_SCAN_ITEMS], sum = 0;
+#pragma unroll
+        for (int k = 0; k < VG_SCAN_ITEMS; ++k) {
+            x[k] = at + k < n ? val[at + k] : 0;
+            sum += x[k];
+        }
+        lds[tid] = sum;
+        __syncthreads();
+        for (int off = 1; off < VG_SCAN_THREADS; off <<= 1) {
+            const long long add = tid >= off ? lds[tid - off] : 0;
+            __syncthreads();
+            lds[tid] += add;
+            __syncthreads();
+        }
+        long long run = carry + lds[tid] - sum;
+        carry += lds[VG_SCAN_THREADS - 1];
+        __syncthreads();  // lds is reused by the next block
+#pragma unroll
+        for (int k = 0; k < VG_SCAN_ITEMS; ++k) {
+            if (at + k < n) val[at + k] = run;
+            run += x[k];
+        }
+    }
+    if (tid == 0) val[n] = carry;
+}
+
+inline dim3 vg_grid(long long n, long long per_block = VG_THREADS) { return dim3((unsigned)((n > 0 ? n : 1) + per_block - 1) / (unsigned)per_block); }
+
+}  // namespace
+
+extern "C" size_t gtsfm_view_graph_workspace_bytes(long long num_edges, long long num_images, long long triplet_capacity) {
+    if (num_edges < 0 || num_images < 0 || triplet_capacity < 0 || num_edges >= VG_MAX_EDGES || num_images >= VG_MAX_IMAGES || triplet_capacity >= VG_MAX_TRIPLETS)
+        return 0;
+    const size_t filter = vg_layout(nullptr, num_edges, num_images, triplet_capacity).bytes, components = vg_cc_layout(nullptr, num_images).bytes;
+    return filter > components ? filter : components;
+}
+
+extern "C" int gtsfm_view_graph_cycle_filter_f64(const int32_t* pair_images_dev, const double* rotation_dev, const uint8_t* pair_enable_dev, long long num_edges,
+                                                 int num_images, int criterion, double error_threshold, long long triplet_capacity, void* workspace_dev,
+                                                 size_t workspace_bytes, int32_t* num_triplets_dev, double* aggregate_error_dev, uint8_t* keep_dev,
+                                                 int32_t* counts_dev, int32_t* triplets_dev, double* cycle_error_dev, long long* num_triplets_host, void* stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    const char* me = "gtsfm_view_graph_cycle_filter_f64";
+    if (num_triplets_host) *num_triplets_host = -1;
+    GTSFM_CHECK_ARG(num_edges >= 0 && num_edges < VG_MAX_EDGES && num_images >= 0 && num_images < VG_MAX_IMAGES && triplet_capacity >= 0 && triplet_capacity < VG_MAX_TRIPLETS,
+                    "%s: sizes out of range (%lld edges, %d images, %lld triplets)", me, num_edges, num_images, triplet_capacity);
+    GTSFM_CHECK_ARG(criterion == 0 || criterion == 1, "%s: criterion %d is neither MIN_EDGE_ERROR (0) nor MEDIAN_EDGE_ERROR (1)", me, criterion);
+    GTSFM_CHECK_ARG(counts_dev, "%s: null counts_dev", me);
+    GTSFM_CHECK_ARG((triplets_dev == nullptr) == (cycle_error_dev == nullptr), "%s: triplets_dev and cycle_error_dev come together", me);
+    if (num_edges == 0) {
+        if (hipMemsetAsync(counts_dev, 0, 8 * sizeof(int32_t), stream) != hipSuccess) {
+            gtsfm_set_error("%s: hipMemsetAsync failed: %s", me, hipGetErrorString(hipGetLastError()));
+            return GTSFM_ERR_HIP;
+        }
+        if (num_triplets_host) *num_triplets_host = 0;
+        return GTSFM_OK;
+    }
+    GTSFM_CHECK_ARG(pair_images_dev && rotation_dev && workspace_dev && num_triplets_dev && aggregate_error_dev && keep_dev, "%s: null pointer", me);
+    GTSFM_CHECK_ARG(((uintptr_t)workspace_dev & 255) == 0, "%s: the workspace must be aligned to 256 bytes", me);
+    VgGraph g{pair_images_dev, rotation_dev, pair_enable_dev, num_edges, num_images, vg_layout(workspace_dev, num_edges, num_images, triplet_capacity)};
+    if (workspace_bytes < g.w.bytes) {
+        gtsfm_set_error("%s: workspace of %zu bytes, %zu needed for %lld edges, %d images and %lld triplets", me, workspace_bytes, g.w.bytes, num_edges, num_images,
+                        triplet_capacity);
+        return GTSFM_ERR_WORKSPACE;
+    }
+    const dim3 threads(VG_THREADS), edge_grid = vg_grid(num_edges), slot_grid = vg_grid(2 * num_edges);
+    const long long init_n = (long long)num_images + 1 > VG_FLAG_WORDS ? (long long)num_images + 1 : VG_FLAG_WORDS;
+
+    hipLaunchKernelGGL(vg_init_kernel, vg_grid(init_n), threads, 0, stream, g, init_n);
+    GTSFM_CHECK_LAUNCH("vg_init_kernel");
+    hipLaunchKernelGGL(vg_edge_degree_kernel, edge_grid, threads, 0, stream, g);
+    GTSFM_CHECK_LAUNCH("vg_edge_degree_kernel");
+    hipLaunchKernelGGL(vg_scan_kernel, dim3(1), dim3(VG_SCAN_THREADS), 0, stream, g.w.row_off, (long long)num_images);
+    GTSFM_CHECK_LAUNCH("vg_scan_kernel");
+    hipLaunchKernelGGL(vg_edge_fill_kernel, edge_grid, threads, 0, stream, g);
+    GTSFM_CHECK_LAUNCH("vg_edge_fill_kernel");
+    hipLaunchKernelGGL(vg_slot_rank_kernel, slot_grid, threads, 0, stream, g);
+    GTSFM_CHECK_LAUNCH("vg_slot_rank_kernel");
+    int flags[2] = {0, 0};
+    if (hipMemcpyAsync(flags, g.w.flags, sizeof(flags), hipMemcpyDeviceToHost, stream) != hipSuccess || hipStreamSynchronize(stream) != hipSuccess) {
+        gtsfm_set_error("%s: building the adjacency failed: %s", me, hipGetErrorString(hipGetLastError()));
+        return GTSFM_ERR_HIP;
+    }
+    GTSFM_CHECK_ARG(!flags[0], "%s: an enabled edge has i1 >= i2 or names an image outside 0 .. %d; nothing was written", me, num_images - 1);
+    GTSFM_CHECK_ARG(!flags[1], "%s: an enabled edge is listed twice; nothing was written", me);
+
+    hipLaunchKernelGGL(vg_slot_triplets_kernel, slot_grid, threads, 0, stream, g, 0, (int*)nullptr, (double*)nullptr);
+    GTSFM_CHECK_LAUNCH("vg_slot_triplets_kernel");
+    hipLaunchKernelGGL(vg_scan_kernel, dim3(1), dim3(VG_SCAN_THREADS), 0, stream, g.w.seg_off, 2 * num_edges);
+    GTSFM_CHECK_LAUNCH("vg_scan_kernel");
+    hipLaunchKernelGGL(vg_scan_kernel, dim3(1), dim3(VG_SCAN_THREADS), 0, stream, g.w.trip_off, 2 * num_edges);
+    GTSFM_CHECK_LAUNCH("vg_scan_kernel");
+    long long totals[2] = {-1, -1};  // entries of the per-edge lists, distinct triplets
+    if (hipMemcpyAsync(&totals[0], g.w.seg_off + 2 * num_edges, 8, hipMemcpyDeviceToHost, stream) != hipSuccess ||
+        hipMemcpyAsync(&totals[1], g.w.trip_off + 2 * num_edges, 8, hipMemcpyDeviceToHost, stream) != hipSuccess || hipStreamSynchronize(stream) != hipSuccess) {
+        gtsfm_set_error("%s: counting the triplets failed: %s", me, hipGetErrorString(hipGetLastError()));
+        return GTSFM_ERR_HIP;
+    }
+    GTSFM_CHECK_ARG(totals[1] >= 0 && totals[0] == 3 * totals[1], "%s: %lld list entries for %lld triplets; nothing was written", me, totals[0], totals[1]);
+    if (num_triplets_host) *num_triplets_host = totals[1];
+    if (totals[1] > triplet_capacity) {
+        gtsfm_set_error("%s: %lld triplets, capacity (workspace and triplet outputs) for %lld; nothing was written", me, totals[1], triplet_capacity);
+        return GTSFM_ERR_WORKSPACE;
+    }
+
+    hipLaunchKernelGGL(vg_slot_triplets_kernel, slot_grid, threads, 0, stream, g, 1, triplets_dev, cycle_error_dev);
+    GTSFM_CHECK_LAUNCH("vg_slot_triplets_kernel");
+    hipLaunchKernelGGL(vg_edge_aggregate_kernel, vg_grid(num_edges, VG_THREADS / VG_WAVE), threads, 0, stream, g, criterion, error_threshold, num_triplets_dev,
+                       aggregate_error_dev, keep_dev);
+    GTSFM_CHECK_LAUNCH("vg_edge_aggregate_kernel");
+    hipLaunchKernelGGL(vg_filter_counts_kernel, dim3(1), dim3(VG_SCAN_THREADS), 0, stream, g.w.input, keep_dev, num_triplets_dev, num_edges, totals[1], counts_dev);
+    GTSFM_CHECK_LAUNCH("vg_filter_counts_kernel");
+    return GTSFM_OK;
+}
+
+extern "C" int gtsfm_largest_component(const int32_t* pair_images_dev, const uint8_t* pair_enable_dev, long long num_edges, int num_images, void* workspace_dev,
+                                       size_t workspace_bytes, uint8_t* node_mask_dev, uint8_t* pair_keep_dev, int32_t* counts_dev, void* stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    const char* me = "gtsfm_largest_component";
+    GTSFM_CHECK_ARG(num_edges >= 0 && num_edges < VG_MAX_EDGES && num_images >= 0 && num_images < VG_MAX_IMAGES, "%s: sizes out of range (%lld edges, %d images)", me,
+                    num_edges, num_images);
+    GTSFM_CHECK_ARG(counts_dev && (num_images == 0 || node_mask_dev) && (num_edges == 0 || (pair_images_dev && pair_keep_dev)), "%s: null pointer", me);
+    GTSFM_CHECK_ARG(workspace_dev && ((uintptr_t)workspace_dev & 255) == 0, "%s: the workspace must be aligned to 256 bytes", me);
+    VgComponents g = vg_cc_layout(workspace_dev, num_images);
+    g.pair_images = pair_images_dev, g.pair_enable = pair_enable_dev, g.num_edges = num_edges, g.num_images = num_images;
+    if (workspace_bytes < g.bytes) {
+        gtsfm_set_error("%s: workspace of %zu bytes, %zu needed for %d images", me, workspace_bytes, g.bytes, num_images);
+        return GTSFM_ERR_WORKSPACE;
+    }
+    const dim3 threads(VG_THREADS), edge_grid = vg_grid(num_edges), node_grid = vg_grid(num_images);
+    const long long init_n = num_images > VG_FLAG_WORDS ? num_images : VG_FLAG_WORDS;
+    hipLaunchKernelGGL(vg_cc_init_kernel, vg_grid(init_n), threads, 0, stream, g, init_n);
+    GTSFM_CHECK_LAUNCH("vg_cc_init_kernel");
+    for (int rounds = 0; num_edges > 0;) {
+        if (rounds == VG_MAX_ROUNDS) {
+            gtsfm_set_error("%s: no fixed point after %d rounds (%d images, %lld edges); nothing was written", me, rounds, num_images, num_edges);
+            return GTSFM_ERR_INVALID;
+        }
+        hipLaunchKernelGGL(vg_cc_hook_kernel, edge_grid, threads, 0, stream, g, rounds);
+        GTSFM_CHECK_LAUNCH("vg_cc_hook_kernel");
+        hipLaunchKernelGGL(vg_cc_compress_kernel, node_grid, threads, 0, stream, g);
+        GTSFM_CHECK_LAUNCH("vg_cc_compress_kernel");
+        int flag[2] = {0, 0};  // bad input, this round hooked
+        if (hipMemcpyAsync(&flag[0], g.flags, sizeof(int), hipMemcpyDeviceToHost, stream) != hipSuccess ||
+            hipMemcpyAsync(&flag[1], g.flags + 8 + rounds, sizeof(int), hipMemcpyDeviceToHost, stream) != hipSuccess || hipStreamSynchronize(stream) != hipSuccess) {
+            gtsfm_set_error("%s: round %d failed: %s", me, rounds, hipGetErrorString(hipGetLastError()));
+            return GTSFM_ERR_HIP;
+        }
+        GTSFM_CHECK_ARG(!flag[0], "%s: an enabled edge names an image outside 0 .. %d; nothing was written", me, num_images - 1);
+        ++rounds;
+        if (!flag[1]) break;
+    }
+    if (num_edges > 0) {
+        hipLaunchKernelGGL(vg_cc_node_count_kernel, node_grid, threads, 0, stream, g);
+        GTSFM_CHECK_LAUNCH("vg_cc_node_count_kernel");
+    }
+    hipLaunchKernelGGL(vg_cc_summary_kernel, dim3(1), dim3(VG_SCAN_THREADS), 0, stream, g, counts_dev);
+    GTSFM_CHECK_LAUNCH("vg_cc_summary_kernel");
+    hipLaunchKernelGGL(vg_cc_write_node_kernel, node_grid, threads, 0, stream, g, node_mask_dev);
+    GTSFM_CHECK_LAUNCH("vg_cc_write_node_kernel");
+    if (num_edges > 0) {
+        hipLaunchKernelGGL(vg_cc_write_edge_kernel, edge_grid, threads, 0, stream, g, pair_keep_dev);
+        GTSFM_CHECK_LAUNCH("vg_cc_write_edge_kernel");
+    }
+    return GTSFM_OK;
+}

@@ -259,6 +259,16 @@ SIGNATURES = {
          C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int, C.c_int, C.c_double, C.c_double, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
     ),
+    "gtsfm_view_graph_workspace_bytes": (C.c_size_t, [C.c_longlong, C.c_longlong, C.c_longlong]),
+    "gtsfm_view_graph_cycle_filter_f64": (
+        C.c_int,
+        [C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong, C.c_int, C.c_int, C.c_double, C.c_longlong, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
+         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_longlong), C.c_void_p],
+    ),
+    "gtsfm_largest_component": (
+        C.c_int,
+        [C.c_void_p, C.c_void_p, C.c_longlong, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
+    ),
 }
 
 

@@ -725,6 +725,54 @@ int gtsfm_two_view_ba_f64(const float* kp_xy_dev, const long long* kp_off1_dev, 
                           void* workspace_dev, size_t workspace_bytes, double* rotation_out_dev, double* translation_out_dev, uint8_t* valid_mask_dev,
                           double* point_dev, double* cost_dev, int32_t* stats_dev, void* stream);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * View-graph estimation: rotation cycle consistency and the largest connected component (float64)
+ *   replaces gtsfm/view_graph_estimator/cycle_consistent_rotation_estimator.py:80-157,224-240 (run, the per-edge aggregate),
+ *   gtsfm/utils/graph.py:92-149 (create_adjacency_list, extract_cyclic_triplets_from_edges), gtsfm/utils/geometry_comparisons.py:137-159,
+ *   226-241 (the cycle error) and gtsfm/utils/graph.py:24-89 (the largest component), called from gtsfm/multi_view_optimizer.py:82-84,
+ *   130-164,175: the configured estimator, once more with MEDIAN_EDGE_ERROR, then prune_to_largest_connected_component.
+ * A vertex is an image; an edge is a row: pair_images_dev [E][2] int32 = (i1, i2), rotation_dev [E][9] float64 = i2Ri1 row-major (what the
+ * verifier and gtsfm_two_view_ba_f64 write), pair_enable_dev [E] uint8 optional (NULL: every row). An edge is an INPUT EDGE when it is
+ * enabled and its nine numbers are finite (the device form of _get_valid_input_edges). An enabled edge with i1 >= i2, an index outside
+ * 0 .. num_images - 1, or the pair of another enabled edge makes the call fail (GTSFM_ERR_INVALID, gtsfm_last_error) with no output written.
+ * For every input edge (a, b), each common neighbour c of a and b over the input edges is a triplet. Its error is the angle in degrees of
+ * M = i2Ri0^T . i2Ri1 . i1Ri0 over the sorted triplet i0 < i1 < i2 (products in that order), found as scipy's
+ * Rotation.from_matrix(M).as_rotvec() norm finds it: matrix -> quaternion by the largest of trace and diagonal, normalised, then
+ * 2 atan2(|q_xyz|, |q_w|). The error of a triplet is the same bytes on its three edges. criterion 0 = MIN_EDGE_ERROR, 1 = MEDIAN_EDGE_ERROR
+ * (numpy's median: the middle element, or (lo + hi) / 2 of the two middle ones); keep = aggregate < error_threshold, strict; an input edge
+ * without a triplet is kept. Every output depends on the SET of input edges and their rotations only: permuting the rows permutes the
+ * per-edge outputs byte for byte and leaves the triplet list unchanged.
+ * PARITY UNPINNED towards the reference: gtsam's Rot3.between / compose arithmetic, restated as float64 matrix products in the stated order;
+ * rotations that are not orthonormal to about 1e-9, where scipy's from_matrix and this routine may part ways; an edge whose aggregate lies
+ * within the measured tolerance of the threshold (profiles/view_graph_gpu_tests.txt), which is kept or dropped by the last bits. The
+ * specification is tests/view_graph_reference.py.
+ * ---------------------------------------------------------------------------------------------------------- */
+
+/* Bytes of device workspace for either call below (0 for sizes out of range: a negative one, 2^28 edges or images, 2^31 / 3 triplets):
+ * about 60 per edge, 12 per image and 24 per triplet of capacity. */
+size_t gtsfm_view_graph_workspace_bytes(long long num_edges, long long num_images, long long triplet_capacity);
+
+/* Per edge row: num_triplets_dev [E] int32, aggregate_error_dev [E] float64 (NaN without a triplet or when not an input edge), keep_dev [E]
+ * uint8 (0 when not an input edge). counts_dev [8] int32: input edges, kept edges, distinct triplets, the largest per-edge triplet count,
+ * 0, 0, 0, 0. triplets_dev [triplet_capacity][3] int32 and cycle_error_dev [triplet_capacity] (both optional, together): each distinct
+ * triplet once, sorted nodes, in lexicographic order; the first counts_dev[2] rows are written.
+ * The call waits for the stream twice: for the two input flags, and for the triplet count T, which it also stores in *num_triplets_host
+ * (optional host pointer; -1 until known). T > triplet_capacity is GTSFM_ERR_WORKSPACE with no output written: repeat with a workspace and
+ * outputs for at least T. num_edges == 0: zero counts, nothing else is touched. */
+int gtsfm_view_graph_cycle_filter_f64(const int32_t* pair_images_dev, const double* rotation_dev, const uint8_t* pair_enable_dev, long long num_edges,
+                                      int num_images, int criterion, double error_threshold, long long triplet_capacity, void* workspace_dev,
+                                      size_t workspace_bytes, int32_t* num_triplets_dev, double* aggregate_error_dev, uint8_t* keep_dev, int32_t* counts_dev,
+                                      int32_t* triplets_dev, double* cycle_error_dev, long long* num_triplets_host, void* stream);
+
+/* The largest connected component of the enabled edges (any order of i1 and i2; i1 == i2 is legal). node_mask_dev [num_images] uint8;
+ * pair_keep_dev [E] uint8: enabled and both endpoints in the component; counts_dev [8] int32: nodes and edges of the component, components
+ * with at least one edge, 0, .... Of components of equal size the one that owns the enabled edge with the smallest row wins, as
+ * max(nx.connected_components(g), key=len) decides after add_edges_from in row order. The labelling runs in rounds of two launches and
+ * reads a 4-byte flag after each, as gtsfm_tracks_from_matches does, and refuses after 64 rounds; an enabled edge that names an image
+ * outside 0 .. num_images - 1 is refused the same way, with no output written. */
+int gtsfm_largest_component(const int32_t* pair_images_dev, const uint8_t* pair_enable_dev, long long num_edges, int num_images, void* workspace_dev,
+                            size_t workspace_bytes, uint8_t* node_mask_dev, uint8_t* pair_keep_dev, int32_t* counts_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
