@@ -221,6 +221,88 @@ class VerifiedScene:
             pruned, component = comp["pair_keep"].cpu().numpy(), comp["counts"]
         return ViewGraph(pairs, keep, pruned, results, component)
 
+    def translation_inliers(self, wRi_list: List[Any], camera_intrinsics: List[Any], edges: Optional[Iterable[Tuple[int, int]]] = None, averaging=None):  # noqa: N803
+        """1DSfM outlier rejection for the scene's edges (the first half of translation averaging, ``gtsfm/multi_view_optimizer.py:175-199``
+        with ``averaging_1dsfm.py:234-315,530-549``) on the launches' unit translations ``t`` and the tracks of ``edges`` (normally
+        ``ViewGraph.edges``; None: every edge) where they lie. ``wRi_list``: a rotation (3 x 3 array or anything with ``.matrix()``) or None
+        per image, whoever computed them; ``camera_intrinsics``: a pure pinhole calibration per image that has one; ``averaging``: a
+        ``TranslationAveraging1DSFM`` (None: its defaults) whose sampling method, track settings and threshold are used. Only ``track_off``
+        and ``image`` are downloaded, for the host's sequential track selection; the track mask and the projection directions are
+        uploaded; counts, masks and the mean weights come back. The two sampling modes that draw from the measurements take one more
+        call, which downloads the world directions. Edges of ``extra`` take part with their uploaded directions. Returns a
+        ``TranslationInliers``: ``.edges`` (the inlier pairs: the ``edges=`` argument of ``tracks()`` and ``triangulate()``),
+        ``.inlier_cameras``, ``.mean_weights``."""
+        from gtsfm_amd.averaging.translation.averaging_1dsfm import TranslationAveraging1DSFM, TranslationInliers, matrix3, select_tracks_csr, vector3
+        from gtsfm_amd.common.calibration import pinhole_parameters
+        from gtsfm_amd.runtime.translation_engine import COUNT_FIELDS
+
+        averaging = averaging or TranslationAveraging1DSFM()
+        if self.feats is None:
+            return TranslationInliers([], np.zeros(0), np.zeros(0, np.uint8), np.zeros(0, np.uint8), np.zeros(0), np.zeros(0, np.uint8), dict.fromkeys(COUNT_FIELDS, 0))
+        import torch
+
+        xy = self.feats["xy"]
+        device, num_images = xy.device, int(xy.shape[0])
+        averaging._device = averaging._device or device
+        engine = averaging.engine()
+        edges = None if edges is None else [(int(a), int(b)) for a, b in edges]
+        wanted = None if edges is None else set(edges)
+        pairs: List[Tuple[int, int]] = [(int(p[0]), int(p[1])) for v in self.launches for p in v["pairs"]]
+        direction =[v["t"].reshape(-1, 3).to(torch.float64) for v in self.launches]
+        enable = [(v["stats"][:, 0] > 0).to(torch.uint8) for v in self.launches]
+        extra = [p for p in self.extra if p in self.verified and self.verified[p][1] is not None]
+        if extra:
+            pairs += [(int(p[0]), int(p[1])) for p in extra]
+            direction.append(torch.from_numpy(np.stack([vector3(self.verified[p][1]) for p in extra])).to(device))
+            enable.append(torch.ones(len(extra), dtype=torch.uint8, device=device))
+        on = torch.cat(enable).contiguous() if enable else torch.empty(0, dtype=torch.uint8, device=device)
+        if wanted is not None and pairs:
+            on = (on * torch.from_numpy(np.array([p in wanted for p in pairs], np.uint8)).to(device)).contiguous()
+        pair_direction = torch.cat(direction).contiguous() if direction else torch.empty((0, 3), dtype=torch.float64, device=device)
+        rotation, rotation_valid, intrinsics = np.zeros((num_images, 9)), np.zeros(num_images, np.uint8), np.ones((num_images, 4))
+        for i in range(num_images):
+            if i < len(wRi_list) and wRi_list[i] is not None:
+                rotation[i], rotation_valid[i] = matrix3(wRi_list[i]).reshape(9), 1
+            if i < len(camera_intrinsics) and camera_intrinsics[i] is not None:
+                *intrinsics[i], pure = pinhole_parameters(camera_intrinsics[i])
+                if not pure:
+                    raise NotImplementedError(f"image {i}: {type(camera_intrinsics[i]).__name__} is not a pure pinhole calibration")
+        # get_valid_measurements_in_world_frame on the host's record of the edges: i1 enters although wRi1 is not looked at
+        live = [p for p in pairs if (wanted is None or p in wanted) and p in self.verified and self.verified[p][1] is not None and rotation_valid[p[1]]]
+        valid_cameras = {c for p in live for c in p}
+        if self._engine is None:
+            from gtsfm_amd.runtime.tracks_engine import TracksEngine
+
+            self._engine = TracksEngine(device)
+        use_tracks = averaging._use_tracks_for_averaging
+        if use_tracks:
+            trk = self._engine.tracks_from_verified(self.launches, int(xy.shape[1]), num_images, edges=edges, extra=self.extra, kp_xy=xy.reshape(-1, 2))
+            track_off, image, uv = trk["track_off"].contiguous(), trk["image"].contiguous(), trk["uv"].contiguous()
+            track_off_host, image_host = track_off.cpu().numpy(), image.cpu().numpy()
+            track_enable, meas_enable = select_tracks_csr(track_off_host, image_host, valid_cameras, use_all_tracks=averaging._use_all_tracks_for_averaging)
+        else:
+            track_off, image = torch.zeros(1, dtype=torch.int64, device=device), torch.empty(0, dtype=torch.int32, device=device)
+            uv = torch.empty((0, 2), dtype=torch.float32, device=device)
+            track_off_host, image_host, track_enable, meas_enable = np.zeros(1, np.int64), np.zeros(0, np.int32), np.zeros(0, np.uint8), np.zeros(0, np.uint8)
+        if not averaging._use_relative_camera_poses:
+            on = torch.zeros_like(on)
+        up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(device)  # noqa: E731
+        args = [up(np.asarray(pairs, np.int32).reshape(-1, 2)), pair_direction, on, up(rotation), up(rotation_valid), up(intrinsics), track_off, image, uv, up(track_enable),
+                up(meas_enable)]
+        capacity = num_images + int(track_enable.sum())
+        methods, world = TranslationAveraging1DSFM.ProjectionSamplingMethod, None
+        if averaging._projection_sampling_method == methods.SAMPLE_WITH_UNIFORM_DENSITY:
+            directions = averaging.sample_projection_directions(np.zeros((0, 3)))
+        else:  # the measurements themselves are sampled: one call for the world directions, which are then given
+            first = engine.inliers(*args, up(np.array([[1.0, 0.0, 0.0]])), threshold=averaging._outlier_weight_threshold, node_capacity=capacity)
+            world = (first["world_pair"], first["world_meas"])
+            combined = np.concatenate([world[0].cpu().numpy(), world[1].cpu().numpy()])
+            directions = averaging.sample_projection_directions(combined[np.isfinite(combined).all(axis=1)])
+        out = engine.inliers(*args, up(np.asarray(directions, np.float64).reshape(-1, 3)), threshold=averaging._outlier_weight_threshold, world=world, node_capacity=capacity)
+        tracks = {"track_off": track_off_host, "image": image_host, "track_enable": track_enable, "meas_enable": meas_enable}
+        return TranslationInliers(pairs, out["pair_weight"].cpu().numpy(), out["pair_inlier"].cpu().numpy(), out["camera_inlier"].cpu().numpy(),
+                                  out["meas_weight"].cpu().numpy(), out["meas_inlier"].cpu().numpy(), out["counts"], tracks)
+
     def tracks(self, edges: Optional[Iterable[Tuple[int, int]]] = None) -> Dict[str, Any]:
         """The feature tracks of the verified correspondences (of ``edges`` only, when given: ``filter_corr_by_idx`` followed by
         ``get_2d_tracks``) as CSR arrays on the host: ``track_off`` [T + 1] int64, ``image`` / ``kp`` [S] int32, ``track_uv`` [S, 2]

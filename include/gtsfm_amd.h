@@ -773,6 +773,51 @@ int gtsfm_view_graph_cycle_filter_f64(const int32_t* pair_images_dev, const doub
 int gtsfm_largest_component(const int32_t* pair_images_dev, const uint8_t* pair_enable_dev, long long num_edges, int num_images, void* workspace_dev,
                             size_t workspace_bytes, uint8_t* node_mask_dev, uint8_t* pair_keep_dev, int32_t* counts_dev, void* stream);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * Translation averaging, first half: 1DSfM outlier rejection (float64)
+ *   replaces gtsfm/averaging/translation/averaging_1dsfm.py:234-315 (compute_inliers, with gtsam's MFAS per projection direction), :403-437
+ *   (_get_landmark_directions) and :684-707 (get_valid_measurements_in_world_frame), called from gtsfm/multi_view_optimizer.py:175-199.
+ * Camera i is node i, track j is node num_images + j. A pair row (i1, i2, i2Ui1) is the measurement (key1, key2) = (i2, i1) with the world
+ * direction unit(wRi2 . i2Ui1); it is VALID when it is enabled (pair_enable_dev, NULL: every row), rotation_valid_dev[i2] is set (i1's
+ * rotation is not looked at, as in the reference) and the three numbers are finite. A track measurement s of track j (track_off_dev [T + 1],
+ * image_dev [S], uv_dev [S][2]: the track builder's CSR) is the measurement (camera, num_images + j) with the direction
+ * unit(wRi . unit(((u - cx) / fx, (v - cy) / fy, 1))) for intrinsics_dev [N][4] = fx, fy, cx, cy; it is valid when track_enable_dev[j] and
+ * meas_enable_dev[s] (NULL: all) are set and the direction is finite. unit(v) = v / sqrt((x x + y y) + z z); a matrix row is summed as
+ * (r0 x + r1 y) + r2 z. With directions_given != 0 the world directions are INPUTS in world_pair_dev / world_meas_dev (valid: enabled and
+ * finite) and rotation, intrinsics, pair_direction and uv are not read.
+ * Per projection direction d (directions_dev [D][3], unit vectors) an edge has w = (mx dx + my dy) + mz dz and runs key1 -> key2 unless
+ * w < 0. MFAS: inW / outW per node are the sums of |w| over its edges in ascending (key1, key2) order; then, one node per step: the
+ * smallest id with inW < 1e-8 if there is one, else the largest (outW + 1) / (inW + 1), ties to the smallest id; the chosen node's |w| is
+ * subtracted from outW of its remaining in-neighbours and inW of its remaining out-neighbours. An edge whose source was chosen after its
+ * destination weighs |w|, else 0; the weights are added over the directions in order and divided by D; inlier = mean < threshold. A pair's
+ * cameras become inlier cameras; a measurement stays an inlier only when its camera is one. Every byte is fixed by the inputs: not by the
+ * grid, the row order of the lists, the storage tier or timing (tests/translation_inliers_reference.py is the specification).
+ * Refused (GTSFM_ERR_INVALID, gtsfm_last_error): an enabled pair row with i1 >= i2 or an id out of range, a measurement listed twice, an
+ * enabled measurement whose camera is out of range or has no valid rotation, D <= 0 with rows present.
+ * PARITY UNPINNED towards the reference: gtsam's MFAS picks among several roots or tied scores in the order of an unordered_map; Unit3's
+ * normalisation in the last bits; calibrations with distortion (not handled); TranslationRecovery (not part of this call).
+ * ---------------------------------------------------------------------------------------------------------- */
+
+/* Bytes of device workspace (0 for sizes out of range). node_capacity: the most nodes that may have an edge (at most num_images +
+ * num_tracks; the host knows num_images + the enabled tracks). lds_node_limit: up to this many graph nodes the MFAS state is kept in LDS,
+ * beyond it in a slice of the workspace per workgroup; negative or more than 2048: 2048. Both tiers give the same bytes. */
+size_t gtsfm_translation_inliers_workspace_bytes(long long num_pairs, long long num_meas, long long num_images, long long num_tracks,
+                                                 long long num_directions, long long node_capacity, int lds_node_limit);
+
+/* Outputs: world_pair_dev [E][3], world_meas_dev [S][3] (NaN rows where not valid), pair_weight_dev [E], meas_weight_dev [S] (the mean
+ * outlier weight, NaN where not valid), pair_inlier_dev [E], meas_inlier_dev [S], camera_inlier_dev [N] uint8, position_dev [D][N + T] int32
+ * (optional: each node's place in the ordering of each direction, -1 for a node without an edge), counts_dev [8] int32: valid pair rows,
+ * valid measurements, nodes with an edge, inlier pairs, inlier measurements, inlier cameras, 0, 0. The call waits for the stream once, for
+ * the refusal flags and the node count; more nodes than node_capacity is GTSFM_ERR_WORKSPACE. */
+int gtsfm_translation_inliers_f64(const int32_t* pair_images_dev, const double* pair_direction_dev, const uint8_t* pair_enable_dev, long long num_pairs,
+                                  const double* rotation_dev, const uint8_t* rotation_valid_dev, const double* intrinsics_dev, int num_images,
+                                  const long long* track_off_dev, const int32_t* image_dev, const float* uv_dev, const uint8_t* track_enable_dev,
+                                  const uint8_t* meas_enable_dev, long long num_tracks, long long num_meas, const double* directions_dev,
+                                  long long num_directions, double threshold, int directions_given, long long node_capacity, int lds_node_limit,
+                                  void* workspace_dev, size_t workspace_bytes, double* world_pair_dev, double* world_meas_dev, double* pair_weight_dev,
+                                  double* meas_weight_dev, uint8_t* pair_inlier_dev, uint8_t* meas_inlier_dev, uint8_t* camera_inlier_dev,
+                                  int32_t* position_dev, int32_t* counts_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,226 @@
+// Stand-alone host build of the 1DSfM kernels' per-lane functions (the TR_HD functions of gtsfm_amd/csrc/translation_kernels.hip: the edge
+// table, the adjacency, the MFAS ordering, the per-row aggregate), for running them on a CPU and under the host sanitizers:
+//
+//   hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off [-Xarch_host -fsanitize=address,undefined] -c tools/translation_inliers_host_main.cpp -o main.o
+//   hipcc [-fsanitize=address,undefined] main.o -o translation_inliers_host
+//   translation_inliers_host scene.bin out.bin
+//
+// scene.bin: int64 {magic, E, S, N, T, D, 1 with pair_enable, 1 with meas_enable, directions_given, 0 x 7}, double {threshold, 0 x 7}, int32
+// pair_images[2 E], double pair_direction[3 E], uint8 pair_enable[E], double rotation[9 N], uint8 rotation_valid[N], double intrinsics[4 N],
+// int64 track_off[T + 1], int32 image[S], float uv[2 S], uint8 track_enable[T], uint8 meas_enable[S], double directions[3 D], double
+// world_pair[3 E], double world_meas[3 S] (read as inputs with directions_given). out.bin: two copies (see below) of double world_pair[3 E],
+// world_meas[3 S], pair_weight[E], meas_weight[S], uint8 pair_inlier[E], meas_inlier[S], camera_inlier[N], int32 position[D (N + T)], counts[8].
+//
+// The stages are the device call's, each a loop over the indices its kernel covers, the prefix sums by a plain loop. They run twice. First
+// every stage walks its indices in ASCENDING order and ONE lane does the whole ordering of a direction, over a workspace and outputs filled
+// with zeros. Then every stage walks its indices in DESCENDING order and the ordering is done by the device's 256-lane partition, the last
+// lane first, over memory filled with 0xFF. The atomics are plain updates here, so the two runs hand out the list slots in opposite orders.
+// The two outputs must be byte-equal (exit status 2 when they are not). Exit status 3: the input is refused, with the reason on stderr; 1:
+// a bad file. Every input array is a heap allocation of its exact size, so a read outside it is a sanitizer report.
+
+#include <stdarg.h>
+#include <stdlib.h>
+#include <string.h>
+
+#include <vector>
+
+#include "../gtsfm_amd/csrc/translation_kernels.hip"
+
+void gtsfm_set_error(const char* fmt, ...) {
+    va_list args;
+    va_start(args, fmt);
+    vfprintf(stderr, fmt, args);
+    va_end(args);
+    fputc('\n', stderr);
+}
+
+namespace {
+
+const long long SCENE_MAGIC = 0x31534e4952544d46ll;  // "FMTRINS1"
+
+struct Scene {
+    long long E, S, N, T, D, has_pair_enable, has_meas_enable, directions_given;
+    double threshold;
+    int *pair_images, *image;
+    double *pair_direction, *rotation, *intrinsics, *directions, *world_pair, *world_meas;
+    uint8_t *pair_enable, *rotation_valid, *track_enable, *meas_enable;
+    long long* track_off;
+    float* uv;
+};
+
+template <class T>
+T* read_array(FILE* f, size_t n, bool* ok) {
+    T* p = (T*)malloc(n ? n * sizeof(T) : 1);  // exact size: the sanitizer sees every read past the end
+    if (!p || (n && fread(p, sizeof(T), n, f) != n)) *ok = false;
+    return p;
+}
+
+bool read_scene(const char* path, Scene& s) {
+    FILE* f = fopen(path, "rb");
+    if (!f) return false;
+    long long head[16];
+    double opts[8];
+    bool ok = fread(head, 8, 16, f) == 16 && fread(opts, 8, 8, f) == 8 && head[0] == SCENE_MAGIC && tr_sizes_ok(head[1], head[2], head[3], head[4], head[5], head[3] + head[4]);
+    if (ok) {
+        s.E = head[1], s.S = head[2], s.N = head[3], s.T = head[4], s.D = head[5], s.has_pair_enable = head[6], s.has_meas_enable = head[7], s.directions_given = head[8];
+        s.threshold = opts[0];
+        const size_t E = s.E, S = s.S, N = s.N, T = s.T, D = s.D;
+        s.pair_images = read_array<int>(f, 2 * E, &ok), s.pair_direction = read_array<double>(f, 3 * E, &ok), s.pair_enable = read_array<uint8_t>(f, E, &ok);
+        s.rotation = read_array<double>(f, 9 * N, &ok), s.rotation_valid = read_array<uint8_t>(f, N, &ok), s.intrinsics = read_array<double>(f, 4 * N, &ok);
+        s.track_off = read_array<long long>(f, T + 1, &ok), s.image = read_array<int>(f, S, &ok), s.uv = read_array<float>(f, 2 * S, &ok);
+        s.track_enable = read_array<uint8_t>(f, T, &ok), s.meas_enable = read_array<uint8_t>(f, S, &ok), s.directions = read_array<double>(f, 3 * D, &ok);
+        s.world_pair = read_array<double>(f, 3 * E, &ok), s.world_meas = read_array<double>(f, 3 * S, &ok);
+    }
+    fclose(f);
+    return ok;
+}
+
+struct Outputs {
+    std::vector<double> world_pair, world_meas, pair_weight, meas_weight;
+    std::vector<uint8_t> pair_inlier, meas_inlier, camera_inlier;
+    std::vector<int> position, counts;
+};
+
+template <class T>
+void fill_vector(std::vector<T>& v, size_t n, int fill) {
+    v.assign(n + 1, T());  // one spare element: data() is never null
+    memset(v.data(), fill, (n + 1) * sizeof(T));
+    v.resize(n);
+}
+
+void exclusive_scan(long long* val, long long n) {
+    long long run = 0;
+    for (long long i = 0; i < n; ++i) {
+        const long long x = val[i];
+        val[i] = run;
+        run += x;
+    }
+    val[n] = run;
+}
+
+template <class F>
+void walk(long long n, bool descending, F f) {
+    if (descending) {
+        for (long long i = n - 1; i >= 0; --i) f(i);
+    } else {
+        for (long long i = 0; i < n; ++i) f(i);
+    }
+}
+
+// 0: done; 3: refused
+int run(const Scene& s, bool descending, int lanes, int fill, Outputs& out) {
+    const long long E = s.E, S = s.S, N = s.N, T = s.T, D = s.D, rows = E + S, nodes = N + T;
+    fill_vector(out.world_pair, 3 * E, fill), fill_vector(out.world_meas, 3 * S, fill), fill_vector(out.pair_weight, E, fill), fill_vector(out.meas_weight, S, fill);
+    fill_vector(out.pair_inlier, E, fill), fill_vector(out.meas_inlier, S, fill), fill_vector(out.camera_inlier, N, fill), fill_vector(out.position, D * nodes, fill);
+    fill_vector(out.counts, 8, fill);
+    if (s.directions_given) {
+        if (E) memcpy(out.world_pair.data(), s.world_pair, 3 * E * 8);
+        if (S) memcpy(out.world_meas.data(), s.world_meas, 3 * S * 8);
+    }
+    if (D <= 0 && rows > 0) {
+        fprintf(stderr, "refused: no projection direction\n");
+        return 3;
+    }
+    if (S > 0 && T <= 0) {
+        fprintf(stderr, "refused: measurements without tracks\n");
+        return 3;
+    }
+    const size_t bytes = tr_layout(nullptr, rows, nodes, D, nodes, 0).bytes;  // lds_node_limit 0: the state slices exist
+    void* ws = aligned_alloc(256, align_up(bytes ? bytes : 1, 256));
+    memset(ws, fill, align_up(bytes ? bytes : 1, 256));
+    TrGraph g{s.pair_images, s.pair_direction, s.has_pair_enable ? s.pair_enable : nullptr, s.rotation, s.rotation_valid, s.intrinsics, s.track_off, s.image, s.uv,
+              s.track_enable, s.has_meas_enable ? s.meas_enable : nullptr, s.directions, E, S, T, D, (int)N, s.directions_given ? 1 : 0, out.world_pair.data(),
+              out.world_meas.data(), tr_layout(ws, rows, nodes, D, nodes, 0)};
+    const long long init_n = nodes + 1 > TR_FLAG_WORDS ? nodes + 1 : TR_FLAG_WORDS;
+    walk(init_n, descending, [&](long long i) { tr_init(g, i, out.camera_inlier.data()); });
+    walk(rows, descending, [&](long long i) { tr_edge_table(g, i); });
+    walk(nodes, descending, [&](long long i) { tr_node_flag(g, i); });
+    exclusive_scan(g.w.row_off, nodes);
+    exclusive_scan(g.w.cid, nodes);
+    walk(nodes + 1, descending, [&](long long i) { tr_node_compact(g, i, nodes); });
+    walk(rows, descending, [&](long long i) { tr_edge_fill(g, i); });
+    walk(2 * rows, descending, [&](long long i) { tr_slot_rank(g, i); });
+    for (int k = 0; k < 4; ++k) {
+        if (g.w.flags[k]) {
+            const char* why[4] = {"a bad pair", "a duplicate measurement", "a camera out of range", "a camera without a rotation"};
+            fprintf(stderr, "refused: %s\n", why[k]);
+            free(ws);
+            return 3;
+        }
+    }
+    const int num_nodes = (int)g.w.cid[nodes];
+    std::vector<TrKey> keys(lanes);
+    walk(D, descending, [&](long long k) {
+        double* base = g.w.state;  // one "workgroup" at a time: the first slice
+        const TrState st = {base, base + num_nodes, base + 2 * (size_t)num_nodes, g.w.pos + k * num_nodes};
+        const double* d = g.directions + 3 * k;
+        walk(lanes, descending, [&](long long lane) { tr_mfas_init_lane(g, st, d, num_nodes, (int)lane, lanes); });
+        for (int step = 0; step < num_nodes; ++step) {
+            walk(lanes, descending, [&](long long lane) { keys[lane] = tr_mfas_lane_best(st, num_nodes, (int)lane, lanes); });
+            TrKey key = keys[descending ? lanes - 1 : 0];
+            walk(lanes, descending, [&](long long lane) { key = tr_key_max(key, keys[lane]); });
+            if (key.id < num_nodes) walk(lanes, descending, [&](long long lane) { tr_mfas_update_lane(g, st, d, key.id, step, (int)lane, lanes); });
+        }
+    });
+    walk(rows, descending, [&](long long i) {
+        tr_row_aggregate(g, i, num_nodes, s.threshold, out.pair_weight.data(), out.meas_weight.data(), out.pair_inlier.data(), out.meas_inlier.data(),
+                         out.camera_inlier.data());
+    });
+    walk(S, descending, [&](long long i) { tr_meas_filter(g, i, out.camera_inlier.data(), out.meas_inlier.data()); });
+    memset(out.counts.data(), 0, 8 * sizeof(int));  // tr_counts_kernel: integer sums over the rows
+    out.counts[2] = num_nodes;
+    walk(E, descending, [&](long long m) { out.counts[0] += g.w.key1[m] >= 0 ? 1 : 0, out.counts[3] += out.pair_inlier[m] ? 1 : 0; });
+    walk(S, descending, [&](long long m) { out.counts[1] += g.w.key1[E + m] >= 0 ? 1 : 0, out.counts[4] += out.meas_inlier[m] ? 1 : 0; });
+    walk(N, descending, [&](long long c) { out.counts[5] += out.camera_inlier[c] ? 1 : 0; });
+    walk(D * nodes, descending, [&](long long i) { tr_position_out(g, i, num_nodes, out.position.data()); });
+    free(ws);
+    return 0;
+}
+
+template <class T>
+bool write_vector(FILE* f, const std::vector<T>& v) {
+    return v.empty() || fwrite(v.data(), sizeof(T), v.size(), f) == v.size();
+}
+
+bool write_outputs(FILE* f, const Outputs& o) {
+    return write_vector(f, o.world_pair) && write_vector(f, o.world_meas) && write_vector(f, o.pair_weight) && write_vector(f, o.meas_weight) &&
+           write_vector(f, o.pair_inlier) && write_vector(f, o.meas_inlier) && write_vector(f, o.camera_inlier) && write_vector(f, o.position) && write_vector(f, o.counts);
+}
+
+template <class T>
+bool same(const std::vector<T>& a, const std::vector<T>& b) {
+    return a.size() == b.size() && (a.empty() || memcmp(a.data(), b.data(), a.size() * sizeof(T)) == 0);
+}
+
+}  // namespace
+
+int main(int argc, char** argv) {
+    if (argc != 3) {
+        fprintf(stderr, "usage: %s scene.bin out.bin\n", argv[0]);
+        return 1;
+    }
+    Scene s{};
+    if (!read_scene(argv[1], s)) {
+        fprintf(stderr, "cannot read %s\n", argv[1]);
+        return 1;
+    }
+    Outputs first, second;
+    int rc = run(s, false, 1, 0x00, first);
+    if (rc == 0) rc = run(s, true, TR_THREADS, 0xFF, second);
+    free(s.pair_images), free(s.pair_direction), free(s.pair_enable), free(s.rotation), free(s.rotation_valid), free(s.intrinsics), free(s.track_off), free(s.image);
+    free(s.uv), free(s.track_enable), free(s.meas_enable), free(s.directions), free(s.world_pair), free(s.world_meas);
+    if (rc) return rc;
+    FILE* f = fopen(argv[2], "wb");
+    if (!f || !write_outputs(f, first) || !write_outputs(f, second) || fclose(f) != 0) {
+        fprintf(stderr, "cannot write %s\n", argv[2]);
+        return 1;
+    }
+    const bool equal = same(first.world_pair, second.world_pair) && same(first.world_meas, second.world_meas) && same(first.pair_weight, second.pair_weight) &&
+                       same(first.meas_weight, second.meas_weight) && same(first.pair_inlier, second.pair_inlier) && same(first.meas_inlier, second.meas_inlier) &&
+                       same(first.camera_inlier, second.camera_inlier) && same(first.position, second.position) && same(first.counts, second.counts);
+    if (!equal) {
+        fprintf(stderr, "the two runs differ\n");
+        return 2;
+    }
+    return 0;
+}
