@@ -3,9 +3,9 @@ tests/translation_inliers_scenes.py: ``position``, the mean weights, the three m
 (tests/translation_inliers_reference.py), and so are the world directions. Should the device's float64 ``sqrt`` / ``/`` not be correctly
 rounded, the MFAS comparison is NOT loosened: the device's own directions are fed to the restatement for it, and the directions are held to
 8 x the restatement's measured distance from an ``np.longdouble`` evaluation (``-s`` prints both numbers:
-profiles/translation_inliers_gpu_tests.txt). The bytes of one direction do not depend on its place in a batch, on the run, or on the storage
-tier. The drop-in's ``compute_inliers`` and ``VerifiedScene.translation_inliers`` on a synthetic scene in the generators' layout equal the
-restatement's edge list, and ``tracks(edges=result.edges)`` equals ``tracks()`` of the same list given by hand."""
+profiles/translation_inliers_gpu_tests.txt). The bytes of one direction do not depend on its place in a batch (a workgroup's second direction
+included, on either tier), on the run, or on the storage tier (2048 nodes are the last graph in LDS, 2049 the first in the workspace). The
+drop-in's ``compute_inliers`` and ``VerifiedScene.translation_inliers`` on a synthetic scene in the generators' layout equal the restatement's edge list, and ``tracks(edges=result.edges)`` equals ``tracks()`` of the same list given by hand."""
 
 import numpy as np
 import pytest
@@ -49,7 +49,8 @@ def longdouble_distance(sc, world_pair) -> float:
 def test_scene_is_byte_equal_to_the_restatement(engine, name):
     sc, exp = scenes.get(name), scenes.expected(name)
     got = run_scene(engine, sc)
-    assert got["tier"] == ("workspace" if name == "tier_workspace" else "lds")
+    limit = 2048 if sc["lds_node_limit"] < 0 else min(sc["lds_node_limit"], 2048)  # TR_LDS_NODES is the default and the most
+    assert got["tier"] == ("workspace" if int(exp["counts"][2]) > limit else "lds")
     same_directions = all(got[k].tobytes() == exp[k].tobytes() for k in ("world_pair", "world_meas"))
     if same_directions:
         scenes.assert_bytes_equal(name, got, exp)
@@ -81,6 +82,15 @@ def test_a_direction_gives_the_same_bytes_alone_and_anywhere_in_a_batch(engine):
     expected = scenes.expected("five_cameras")["position"]
     tail = run_scene(engine, five, directions=five["directions"][1990:])["position"]
     assert tail.tobytes() == expected[1990:].tobytes()
+    # 770 directions on 768 workgroups, on the workspace tier and with more than 256 nodes on the LDS tier: the rows that workgroups 0 and 1
+    # walk second (768, 769) equal the same directions run alone, as do a first row and the last workgroup's
+    for name, tier in (("directions_770_workspace", "workspace"), ("tier_770", "lds")):
+        sc = scenes.get(name)
+        whole = run_scene(engine, sc)
+        assert whole["tier"] == tier and whole["position"].tobytes() == scenes.expected(name)["position"].tobytes()
+        for k in (0, 767, 768, 769):
+            alone = run_scene(engine, sc, directions=sc["directions"][k:k + 1])
+            assert alone["tier"] == tier and alone["position"].tobytes() == whole["position"][k:k + 1].tobytes(), f"{name}: direction {k} alone differs from its row in the batch"
 
 
 def test_runs_and_storage_tiers_give_the_same_bytes(engine):
@@ -93,6 +103,17 @@ def test_runs_and_storage_tiers_give_the_same_bytes(engine):
         a, b = run_scene(engine, sc, lds_nodes=0), run_scene(engine, sc)
         assert (a["tier"], b["tier"]) == ("workspace", "lds")
         scenes.assert_bytes_equal(name, a, b)
+    # TR_LDS_NODES nodes and one more, with the default limit: 2048 nodes are the largest LDS launch and go to the workspace when forced; 2049
+    # go to the workspace by themselves, and no limit puts them into LDS (a larger one is clamped), so their other run is the limit 0
+    sc = scenes.get("window_2048_2")
+    a, b = run_scene(engine, sc), run_scene(engine, sc, lds_nodes=0)
+    assert (a["tier"], b["tier"]) == ("lds", "workspace")
+    scenes.assert_bytes_equal("window_2048_2", b, a)
+    sc = scenes.get("window_2049_2")
+    a, b, c = run_scene(engine, sc), run_scene(engine, sc, lds_nodes=0), run_scene(engine, sc, lds_nodes=4096)
+    assert (a["tier"], b["tier"], c["tier"]) == ("workspace", "workspace", "workspace")
+    scenes.assert_bytes_equal("window_2049_2", b, a)
+    scenes.assert_bytes_equal("window_2049_2", c, a)
 
 
 @pytest.mark.parametrize("case", ["reversed", "duplicate", "out_of_range", "duplicate_measurement", "camera_without_rotation", "no_direction"])

@@ -104,6 +104,42 @@ def test_cycle_angle_against_scipy_and_50_digits():
     assert small.sum() > 20 and np.abs(got - exact)[small].max() < 1e-13 < 1e-9 < np.abs(via_acos - exact)[small].max()
 
 
+def test_rotations_that_are_not_orthonormal_follow_the_definition_not_scipy():
+    """The numbers behind the PARITY UNPINNED sentence of include/gtsfm_amd.h: scipy's from_matrix re-orthogonalises, the stated definition
+    takes the matrix as it is. On 30 degrees scaled by 1.01 scipy answers 30.000 and the definition 30.076; scipy raises on a non-positive
+    determinant where the definition answers; on hard_cycles_skewed (rows times 1 + N(0, 1e-6)) the two differ by about 1e-4 degrees while the
+    restatement stays within 2.9e-14 degrees of the 50-digit evaluation of the definition."""
+    from scipy.spatial.transform import Rotation
+
+    eye = np.eye(3)
+    scaled = scenes.axis_angle((0.36, 0.48, 0.8), 30.0) * 1.01
+    via_scipy = np.rad2deg(Rotation.from_matrix(scaled).magnitude())
+    defined, exact = ref.cycle_errors(scaled[None], eye[None], eye[None])[0], ref.cycle_error_mp(scaled, eye, eye)
+    print(f"30 degrees scaled by 1.01: scipy {via_scipy:.3f}, the definition {defined:.3f} degrees (50 digits {exact:.3f})")
+    assert f"{via_scipy:.3f}" == "30.000" and f"{defined:.3f}" == f"{exact:.3f}" == "30.076" and abs(defined - exact) < 1e-13
+    mirror = np.diag([1.0, 1.0, -1.0])
+    with pytest.raises(ValueError, match="Non-positive determinant"):
+        Rotation.from_matrix(mirror)
+    assert ref.cycle_errors(mirror[None], eye[None], eye[None])[0] == ref.cycle_error_mp(mirror, eye, eye) == 180.0
+    skewed = scenes.measured_tolerance("hard_cycles_skewed")
+    print(f"hard_cycles_skewed: M M^T off the identity by {skewed['orthonormality']:.3e}; scipy differs from the restatement by {skewed['scipy']:.3e} degrees, "
+          f"the restatement from 50 digits by {skewed['restatement']:.3e} degrees")
+    assert 5e-5 < skewed["scipy"] < 2e-4 and skewed["restatement"] < 1e-13
+
+
+def test_hard_scenes_keep_their_own_tolerance():
+    """The first scenes' measured distance is the one recorded with them (measured_tolerance asserts it) and no hard scene enters it; each hard
+    scene is held to 8 x its own distance over all its triplets."""
+    first = scenes.measured_tolerance()
+    assert f"{first['restatement']:.3e}" == scenes.FIRST_SCENES_RESTATEMENT and first["tolerance"] == 8 * first["restatement"]
+    assert {k[6:] for k in first if k.startswith("scene:")} <= set(scenes.FIRST_SCENES)
+    for name in scenes.HARD_SCENES:
+        tol = scenes.measured_tolerance(name)
+        print(f"{name}: " + ", ".join(f"{k} {v}" for k, v in tol.items()))
+        assert tol["tolerance"] == 8 * tol["restatement"] and tol["exact_zero"]
+    assert scenes.measured_tolerance("hard_cycles")["restatement"] > first["restatement"]  # it would have loosened the first scenes' tolerance
+
+
 def test_median_and_min_are_numpys():
     sc = {s["name"]: s for s in scenes.all_scenes()}["hubs"]
     for criterion, fn in ((ref.MIN_EDGE_ERROR, np.amin), (ref.MEDIAN_EDGE_ERROR, np.median)):

@@ -73,13 +73,15 @@ def run_program(program, sc, criterion, threshold, expect_status=0):
 @pytest.mark.parametrize("name", scenes.SCENE_NAMES)
 def test_host_build_against_the_restatement(program, name):
     sc = {s["name"]: s for s in scenes.all_scenes()}[name]
-    tol = scenes.measured_tolerance()
+    tol = scenes.measured_tolerance(name)  # a hard scene is held to its own measured distance, every other scene to that of the first scenes
     for criterion in (ref.MIN_EDGE_ERROR, ref.MEDIAN_EDGE_ERROR):
         for thr in sc["thresholds"]:
             got = run_program(program, sc, criterion, thr)
-            dist = scenes.check_outputs(f"{name}/{criterion}/{thr}", got, scenes.expected(sc, criterion, thr), tol["tolerance"])
+            dist = scenes.check_outputs(f"{name}/{criterion}/{thr}", got, scenes.expected(sc, criterion, thr), tol["tolerance"], exact_zero=tol["exact_zero"])
             print(f"{name} criterion {criterion} threshold {thr:.6g}: {len(sc['pair_images'])} edges, {int(got['total'][0])} triplets, aggregate within {dist['aggregate_error']:.3e}, "
                   f"cycle error within {dist['cycle_error']:.3e} degrees (restatement from 50 digits {tol['restatement']:.3e}, tolerance {tol['tolerance']:.3e})")
+    if name in scenes.HARD_SCENES:
+        print(f"{name}: " + ", ".join(f"{k} {v}" for k, v in tol.items() if k not in ("restatement", "tolerance", "exact_zero")))
 
 
 @pytest.mark.parametrize("case", ["reversed", "duplicate", "out_of_range", "negative"])

@@ -159,7 +159,10 @@ def build_edges(pair_images, w_pair, pair_valid, track_off, image, w_meas, meas_
 
 def mfas_positions(key1: np.ndarray, key2: np.ndarray, m: np.ndarray, d: np.ndarray, num_nodes: int, return_branches: bool = False):
     """gtsam's MFAS::computeOrdering for one unit projection direction over edges in ascending (key1, key2) order: position [num_nodes] int32,
-    -1 for nodes without an edge. With ``return_branches`` also the number of steps that took the score branch."""
+    -1 for nodes without an edge. With ``return_branches`` also a dict of what the steps did: ``score_steps`` (steps that took the score branch),
+    ``tied_score_steps`` (score steps whose largest score two or more live nodes held), ``epsilon_roots`` (root steps whose root had inW != 0,
+    what subtraction left or an incoming weight below ROOT_EPSILON), ``score_choices`` (the nodes the score steps chose, in order) and
+    ``epsilon_root_in_w`` (the inW of the epsilon roots)."""
     w = project(m, d)
     a = np.abs(w)
     forward = ~(w < 0)  # includes +-0, as gtsam's weight >= 0
@@ -174,14 +177,18 @@ def mfas_positions(key1: np.ndarray, key2: np.ndarray, m: np.ndarray, d: np.ndar
     alive = np.zeros(num_nodes, bool)
     alive[key1], alive[key2] = True, True
     position = np.full(num_nodes, -1, np.int32)
-    score_steps = 0
+    tied_score_steps, score_choices, epsilon_root_in_w = 0, [], []
     for step in range(int(alive.sum())):
         roots = alive & (in_w < ROOT_EPSILON)
         if roots.any():
             choice = int(np.argmax(roots))
+            if in_w[choice] != 0:
+                epsilon_root_in_w.append(float(in_w[choice]))
         else:
-            choice = int(np.argmax(np.where(alive, (out_w + 1.0) / (in_w + 1.0), -np.inf)))
-            score_steps += 1
+            score = np.where(alive, (out_w + 1.0) / (in_w + 1.0), -np.inf)
+            choice = int(np.argmax(score))
+            score_choices.append(choice)
+            tied_score_steps += int((score == score[choice]).sum() > 1)
         position[choice] = step
         alive[choice] = False
         for nbr, e in adj[choice]:
@@ -190,7 +197,9 @@ def mfas_positions(key1: np.ndarray, key2: np.ndarray, m: np.ndarray, d: np.ndar
                     out_w[nbr] = out_w[nbr] - a[e]
                 else:
                     in_w[nbr] = in_w[nbr] - a[e]
-    return (position, score_steps) if return_branches else position
+    branches = {"score_steps": len(score_choices), "tied_score_steps": tied_score_steps, "epsilon_roots": len(epsilon_root_in_w),
+                "score_choices": np.asarray(score_choices, np.int64), "epsilon_root_in_w": np.asarray(epsilon_root_in_w, np.float64)}
+    return (position, branches) if return_branches else position
 
 
 def mfas_positions_brute_force(key1, key2, m, d, num_nodes: int) -> np.ndarray:
@@ -254,8 +263,8 @@ def translation_inliers(pair_images, pair_direction, pair_enable, rotation, rota
     total = np.zeros(len(g["row"]))
     branches = []
     for k, d in enumerate(directions):
-        position[k], sc = mfas_positions(g["key1"], g["key2"], g["m"], d, nodes, return_branches=True)
-        branches.append(sc)
+        position[k], taken = mfas_positions(g["key1"], g["key2"], g["m"], d, nodes, return_branches=True)
+        branches.append(taken)
         total = total + outlier_weights(g["key1"], g["key2"], g["m"], d, position[k])
     mean = np.full(e + s, np.nan)
     if len(g["row"]):
@@ -273,7 +282,9 @@ def translation_inliers(pair_images, pair_direction, pair_enable, rotation, rota
     out = {"world_pair": w_pair, "world_meas": w_meas, "pair_weight": mean[:e], "meas_weight": mean[e:], "pair_inlier": pair_inlier.astype(np.uint8),
            "meas_inlier": meas_inlier.astype(np.uint8), "camera_inlier": camera_inlier.astype(np.uint8), "position": position, "counts": counts, "graph": g}
     if want_branches:
-        out["score_steps"] = np.asarray(branches, np.int64)
+        for key in ("score_steps", "tied_score_steps", "epsilon_roots"):
+            out[key] = np.asarray([b[key] for b in branches], np.int64)
+        out["score_choices"], out["epsilon_root_in_w"] = [b["score_choices"] for b in branches], [b["epsilon_root_in_w"] for b in branches]
     return out
 
 

@@ -181,8 +181,72 @@ def direction_counts(d: int) -> Dict[str, object]:
     return scene(f"directions_{d}", pairs, t, n, random_units(rng, d), rotation=rot, tracks=tracks, uv=rng.uniform(0, 100, size=(12, 2)))
 
 
+def triangles_400(tied: bool) -> Dict[str, object]:
+    """World directions given: 400 disjoint directed triangles a -> a + 1 -> a + 2 -> a on e_x (nodes 0 .. 1199: a lane of the MFAS kernel owns up
+    to five), projected on e_x and e_y. Every triangle costs one score step on e_x and none on e_y (all weights 0: every node is a root).
+    ``tied``: all weights exactly 1, so every score step is a tie among all nodes of the unbroken triangles and the smallest id must win across
+    the four waves and the nodes of a lane. Otherwise the weights are U(0.2, 1): the scores are distinct and the winner is anywhere in the id range."""
+    rng = np.random.default_rng(41)
+    ex, ey, _ = np.eye(3)
+    pairs, m = [], []
+    for a in range(0, 1200, 3):  # (i1, i2) runs i2 -> i1 for w >= 0
+        pairs += [(a, a + 1), (a + 1, a + 2), (a, a + 2)]
+        m += [-ex, -ex, ex]
+    m = np.asarray(m) * (1.0 if tied else rng.uniform(0.2, 1.0, size=(len(pairs), 1)))
+    return scene(f"triangles_400_{'tied' if tied else 'random'}", pairs, np.zeros((len(pairs), 3)), 1200, [ex, ey], world=(m, np.zeros((0, 3))))
+
+
+WINDOW_1100_SEED = 3  # its walk takes roots with 0 < |inW| < 1e-8, left over from subtraction: expected() asserts it
+
+
+def window_1100_3() -> Dict[str, object]:
+    """True geometry with direction noise on a window graph: lanes own four or five nodes, root steps and score steps alternate by the hundred."""
+    rng = np.random.default_rng(WINDOW_1100_SEED)
+    n = 1100
+    centre, rot, _, _ = true_geometry(rng, n, 0)
+    pairs = window(n, 3)
+    t = ref.unit(pair_directions(centre, rot, pairs) + rng.normal(scale=0.5, size=(len(pairs), 3)))
+    return scene("window_1100_3", pairs, t, n, random_units(rng, 2), rotation=rot)
+
+
+def window_tier_boundary(n: int) -> Dict[str, object]:
+    """TR_LDS_NODES = 2048 nodes and one more, with the default lds_node_limit: the largest dynamic-LDS launch and the first graph that goes to
+    the workspace by itself."""
+    rng = np.random.default_rng(n)
+    centre, rot, _, _ = true_geometry(rng, n, 0)
+    pairs = window(n, 2)
+    t = ref.unit(pair_directions(centre, rot, pairs) + rng.normal(scale=0.5, size=(len(pairs), 3)))
+    return scene(f"window_{n}_2", pairs, t, n, random_units(rng, 2), rotation=rot)
+
+
+MANY_DIRECTIONS = 770  # more than the 768 workgroups of the MFAS kernel: workgroups 0 and 1 walk a second direction
+
+
+def many_directions(name: str) -> Dict[str, object]:
+    """An existing graph with 770 seeded directions: directions_770_workspace is the 13-node directions_* graph on the workspace tier, tier_770 the
+    300-node tiers() graph on the LDS tier."""
+    sc = dict(direction_counts(7) if name == "directions_770_workspace" else tiers(2048))
+    sc["name"], sc["directions"] = name, random_units(np.random.default_rng(43), MANY_DIRECTIONS)
+    sc["lds_node_limit"] = 0 if name == "directions_770_workspace" else -1
+    return sc
+
+
+ROOT_EPSILON_TWINS = (5e-9, 2e-8, 1e-8)  # the weight of the edge into the lower camera of twin k (cameras 2 k, 2 k + 1)
+
+
+def root_epsilon() -> Dict[str, object]:
+    """World directions given, projected on e_x: three components of two cameras, the edge pointing into the lower-numbered one with weight 5e-9,
+    2e-8 and exactly 1e-8. inW < 1e-8 is strict: only the first lower camera is a root despite its incoming edge and goes before its twin."""
+    pairs = [(2 * k, 2 * k + 1) for k in range(len(ROOT_EPSILON_TWINS))]
+    m = np.asarray([[x, 0.6, 0.8] for x in ROOT_EPSILON_TWINS])
+    return scene("root_epsilon", pairs, np.zeros((len(pairs), 3)), 2 * len(pairs), [[1.0, 0.0, 0.0]], world=(m, np.zeros((0, 3))))
+
+
+NEW_SCENE_NAMES = ["triangles_400_tied", "triangles_400_random", "window_1100_3", "window_2048_2", "window_2049_2", "directions_770_workspace", "tier_770", "root_epsilon"]
 SCENE_NAMES = (["empty", "one_edge", "five_cameras"] + [f"{kind}_{n}" for n in (63, 64, 65, 255, 256, 257, 513) for kind in ("chain", "ring")] +
-               ["hub_300", "lost_camera", "axis_aligned", "cyclic_conflicts", "gaps_and_invalid", "directions_1", "directions_7", "directions_65", "tier_lds", "tier_workspace"])
+               ["hub_300", "lost_camera", "axis_aligned", "cyclic_conflicts", "gaps_and_invalid", "directions_1", "directions_7", "directions_65", "tier_lds", "tier_workspace"] +
+               NEW_SCENE_NAMES)
+BRUTE_FORCE = ("triangles_400_tied", "triangles_400_random", "window_1100_3", "directions_770_workspace", "tier_770", "root_epsilon")  # one direction each
 
 
 @lru_cache(maxsize=None)
@@ -196,8 +260,16 @@ def get(name: str) -> Dict[str, object]:
     if name.startswith(("chain_", "ring_")):
         kind, n = name.split("_")
         return chain_or_ring(int(n), kind == "ring", seed=int(n))
+    if name in ("directions_770_workspace", "tier_770"):
+        return many_directions(name)
     if name.startswith("directions_"):
         return direction_counts(int(name.split("_")[1]))
+    if name.startswith("triangles_400_"):
+        return triangles_400(name.endswith("_tied"))
+    if name in ("window_2048_2", "window_2049_2"):
+        return window_tier_boundary(int(name.split("_")[1]))
+    if name in ("window_1100_3", "root_epsilon"):
+        return {"window_1100_3": window_1100_3, "root_epsilon": root_epsilon}[name]()
     return {"hub_300": hub, "lost_camera": lost_camera, "axis_aligned": axis_aligned, "cyclic_conflicts": cyclic_conflicts, "gaps_and_invalid": gaps_and_invalid,
             "tier_lds": lambda: tiers(2048), "tier_workspace": lambda: tiers(128)}[name]()
 
@@ -237,10 +309,45 @@ def expected(name: str) -> Dict[str, np.ndarray]:
         on = np.isfinite(out["pair_weight"])
         assert on.tolist() == [1, 1, 1, 0, 1, 0, 1, 1, 0, 1, 1, 1, 1] and c["measurement_edges"] == 8 and c["nodes"] == 12 - 3 + 3
         assert (out["position"][:, [3, 7, 8, 12 + 1]] == -1).all()
+    elif name in ("directions_770_workspace", "tier_770"):
+        # more directions than the MFAS kernel has workgroups, on either tier; the second walk is not a repeat of the first
+        assert len(sc["directions"]) == MANY_DIRECTIONS > 768 and c["nodes"] == (13 if name == "directions_770_workspace" else 300) and steps.max() > 0
+        assert (sc["lds_node_limit"] == 0) == (name == "directions_770_workspace") and c["inlier_pairs"] > 0
+        assert (out["position"][768] != out["position"][0]).any() and (out["position"][769] != out["position"][1]).any()
     elif name.startswith("directions_"):
         assert len(sc["directions"]) == int(name.split("_")[1]) and c["nodes"] == 13 and c["inlier_pairs"] > 0 and steps.max() > 0
     elif name.startswith("tier_"):
         assert c["nodes"] == 300 and (sc["lds_node_limit"] < 300) == (name == "tier_workspace")
+    elif name.startswith("triangles_400_"):
+        chosen = out["score_choices"][0]
+        assert c["nodes"] == 1200 and steps.tolist() == [400, 0] and sc["lds_node_limit"] == -1
+        if name == "triangles_400_tied":
+            # every score step is a tie among all nodes of the unbroken triangles: the smallest id wins, so triangle k is walked at steps 3 k ..
+            assert out["tied_score_steps"].tolist() == [400, 0] and c["inlier_pairs"] == 800
+            assert (out["position"][0][0:1200:3] == np.arange(0, 1200, 3)).all() and chosen.tolist() == list(range(0, 1200, 3))
+        else:
+            # distinct scores: the winners are anywhere in the id range, in every wave and at every depth of a lane's node list
+            assert out["tied_score_steps"].tolist() == [0, 0] and (np.diff(chosen) < 0).sum() > 100 and (np.diff(chosen) > 0).sum() > 100
+            assert set((chosen % 256 // 64).tolist()) == {0, 1, 2, 3} and set((chosen // 256).tolist()) == {0, 1, 2, 3, 4}
+            assert 800 < c["inlier_pairs"] < 1200
+    elif name == "window_1100_3":
+        leftovers = np.concatenate(out["epsilon_root_in_w"])
+        assert c["nodes"] == 1100 and c["pair_edges"] == 3294 and steps.min() > 200 and (c["nodes"] - steps).min() > 200
+        assert ((leftovers != 0) & (np.abs(leftovers) < ref.ROOT_EPSILON)).any(), "no root with 0 < |inW| < 1e-8 left over from subtraction: choose another seed"
+        assert all(len(set((ch // 256).tolist())) >= 4 for ch in out["score_choices"])  # score steps won at the fourth and fifth node of a lane
+    elif name in ("window_2048_2", "window_2049_2"):
+        assert c["nodes"] == int(name.split("_")[1]) and sc["lds_node_limit"] == -1 and steps.min() > 100
+        assert all((ch >= 2048 - 256).any() for ch in out["score_choices"])  # a score step won by a lane's last node
+    elif name == "root_epsilon":
+        p = out["position"][0]
+        assert ROOT_EPSILON_TWINS[0] < ref.ROOT_EPSILON == ROOT_EPSILON_TWINS[2] < ROOT_EPSILON_TWINS[1]
+        assert p[0] < p[1] and p[2] > p[3] and p[4] > p[5], p  # the root despite its edge goes first; 2e-8 and exactly 1e-8 (strict <) wait for their twins
+        assert out["epsilon_roots"][0] >= 1 and out["epsilon_root_in_w"][0].tolist() == [5e-9] and steps[0] == 0
+        assert out["pair_weight"].tolist() == [5e-9, 0.0, 0.0]
+    if name in BRUTE_FORCE:
+        g = out["graph"]
+        brute = ref.mfas_positions_brute_force(g["key1"], g["key2"], g["m"], sc["directions"][0], len(out["position"][0]))
+        assert brute.tobytes() == out["position"][0].tobytes(), f"{name}: the restatement's positions differ from the brute-force ordering on direction 0"
     return out
 
 

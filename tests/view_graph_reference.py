@@ -65,9 +65,10 @@ def extract_triplets(edges: np.ndarray) -> np.ndarray:
     return nodes[trip].astype(np.int64).reshape(-1, 3)
 
 
-def cycle_errors(i1Ri0: np.ndarray, i2Ri1: np.ndarray, i2Ri0: np.ndarray) -> np.ndarray:  # noqa: N803
+def cycle_errors(i1Ri0: np.ndarray, i2Ri1: np.ndarray, i2Ri0: np.ndarray, return_choice: bool = False):  # noqa: N803
     """The angle in degrees of M = i2Ri0^T . i2Ri1 . i1Ri0 for stacks [T, 3, 3], products in that order: matrix -> quaternion by the largest of
-    the diagonal and the trace (the first largest), normalised, then 2 atan2(|q_xyz|, |q_w|)."""
+    the diagonal and the trace (the first largest), normalised, then 2 atan2(|q_xyz|, |q_w|). With ``return_choice`` also which of
+    (m00, m11, m22, trace) decided, [T] in 0 .. 3."""
     r10, r21, r20 = (np.asarray(x, np.float64).reshape(-1, 3, 3) for x in (i1Ri0, i2Ri1, i2Ri0))
     m = np.matmul(np.matmul(r20.transpose(0, 2, 1), r21), r10)
     t = len(m)
@@ -90,11 +91,12 @@ def cycle_errors(i1Ri0: np.ndarray, i2Ri1: np.ndarray, i2Ri0: np.ndarray) -> np.
     q[sel, 3] = 1 + trace[sel]
     q = q / np.sqrt(q[:, 0] * q[:, 0] + q[:, 1] * q[:, 1] + q[:, 2] * q[:, 2] + q[:, 3] * q[:, 3])[:, None]
     angle = 2 * np.arctan2(np.sqrt(q[:, 0] * q[:, 0] + q[:, 1] * q[:, 1] + q[:, 2] * q[:, 2]), np.abs(q[:, 3]))
-    return np.rad2deg(angle)
+    return (np.rad2deg(angle), choice) if return_choice else np.rad2deg(angle)
 
 
-def cycle_error_mp(i1Ri0: np.ndarray, i2Ri1: np.ndarray, i2Ri0: np.ndarray, digits: int = 50) -> float:  # noqa: N803
-    """The same definition for ONE triplet with ``digits`` digits; returned rounded to float64."""
+def cycle_error_mp(i1Ri0: np.ndarray, i2Ri1: np.ndarray, i2Ri0: np.ndarray, digits: int = 50, return_choice: bool = False):  # noqa: N803
+    """The same definition for ONE triplet with ``digits`` digits; returned rounded to float64. With ``return_choice`` also which of
+    (m00, m11, m22, trace) decided: the first largest."""
     import mpmath as mp
 
     with mp.workdps(digits):
@@ -115,7 +117,7 @@ def cycle_error_mp(i1Ri0: np.ndarray, i2Ri1: np.ndarray, i2Ri0: np.ndarray, digi
         norm = mp.sqrt(sum(x * x for x in q))
         q = [x / norm for x in q]
         angle = 2 * mp.atan2(mp.sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2]), abs(q[3]))
-        return float(angle * 180 / mp.pi)
+        return (float(angle * 180 / mp.pi), choice) if return_choice else float(angle * 180 / mp.pi)
 
 
 def triplet_rotations(triplets: np.ndarray, row_of: Dict[Tuple[int, int], int], rotation: np.ndarray):
@@ -206,6 +208,15 @@ def create_adjacency_list(edges: Sequence[Tuple[int, int]]) -> Dict[int, set]:
         adj.setdefault(a, set()).add(b)
         adj.setdefault(b, set()).add(a)
     return adj
+
+
+def create_components(edges: Sequence[Tuple[int, int]]) -> List[set]:
+    """The connected components (node sets) of an edge list, by networkx."""
+    import networkx as nx
+
+    graph = nx.Graph()
+    graph.add_edges_from([tuple(p) for p in np.asarray(edges, np.int64).reshape(-1, 2).tolist()])
+    return list(nx.connected_components(graph))
 
 
 def normalised_edges(edges: Sequence[Tuple[int, int]]) -> np.ndarray:
