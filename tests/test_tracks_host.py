@@ -16,11 +16,13 @@ SCENE_FIGURES = {
     "giant": (3600, 2640, 205, 30, 6, None, 5),
     "zig96": (768, 760, 8, 0, 96, 96, 6),
     "zig1000": (2000, 1998, 2, 0, 1000, 1000, 8),
+    "wide60": (300000, 1534450, 14523, 2345, 35, 218, 5),
 }
 
 
 def build_scene(name):
-    return {"rand24": TR.scene_rand, "giant": TR.scene_giant, "zig96": lambda: TR.scene_zigzag(96, 8), "zig1000": lambda: TR.scene_zigzag(1000, 2)}[name]()
+    return {"rand24": TR.scene_rand, "giant": TR.scene_giant, "zig96": lambda: TR.scene_zigzag(96, 8), "zig1000": lambda: TR.scene_zigzag(1000, 2),
+            "wide60": lambda: TR.scene_rand(num_images=60, num_kp=5000, num_points=40000, seed=3)}[name]()
 
 
 def test_restatement_reproduces_the_four_known_answers():
@@ -64,6 +66,8 @@ def test_gpu_scenes_have_the_stated_properties(name):
         assert ref["tracks"] > 500 and ref["discarded"] > 100 and rows > 64 * 256
     if name == "giant":  # the pigeonhole path: one set far above the image count, and sets that are discarded by the neighbour check too
         assert ref["largest_component"] > 50 * len(sizes)
+    if name == "wide60":  # the workload's node count: more than 256 scan blocks of 1024, so the scan of the block sums takes its second trip
+        assert nodes > 256 * 1024
     if name.startswith("zig"):  # longer than a wavefront; the labels alternate, so one round cannot finish
         assert ref["longest"] == len(sizes) > 64
 
