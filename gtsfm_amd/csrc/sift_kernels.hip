@@ -388,6 +388,16 @@ __global__ __launch_bounds__(256) void sift_refine_kernel(const float* __restric
     kps[idx] = kp;
 }
 
+// The angle (degrees) of a peak at bin j of the smoothed histogram from its neighbours hl, hr: the parabola's vertex, wrapped into
+// [0, 36) bins, 360 - 10 bin, and an angle of 360 is 0.
+__device__ __forceinline__ float sift_peak_angle(int j, float hl, float hs, float hr) {
+    float bin = (float)j + 0.5f * (hl - hr) / (hl - 2.0f * hs + hr);
+    bin = bin < 0.0f ? 36.0f + bin : bin >= 36.0f ? bin - 36.0f : bin;
+    float angle = 360.0f - (360.0f / 36.0f) * bin;
+    if (fabsf(angle - 360.0f) < FLT_EPSILON) angle = 0.0f;
+    return angle;
+}
+
 // One wave per keypoint (64 threads). counts[2] counts every oriented keypoint, written or not. mask: [H0][W0] uint8 or null.
 __global__ __launch_bounds__(64) void sift_orient_kernel(const float* __restrict__ pyr, SiftGeom geom, const SiftKp* __restrict__ kps, int kp_cap,
                                                        const uint8_t* __restrict__ mask, int H0, int W0, int* __restrict__ counts,
@@ -454,10 +464,7 @@ __global__ __launch_bounds__(64) void sift_orient_kernel(const float* __restrict
         const float hl = sm[(lane + 35) % 36], hr = sm[(lane + 1) % 36];
         if (hs > hl && hs > hr && hs >= thr) {
             peak = true;
-            float bin = (float)lane + 0.5f * (hl - hr) / (hl - 2.0f * hs + hr);
-            bin = bin < 0.0f ? 36.0f + bin : bin >= 36.0f ? bin - 36.0f : bin;
-            angle = 360.0f - (360.0f / 36.0f) * bin;
-            if (fabsf(angle - 360.0f) < FLT_EPSILON) angle = 0.0f;
+            angle = sift_peak_angle(lane, hl, hs, hr);
         }
     }
     const unsigned long long peaks = __ballot(peak);
@@ -612,6 +619,43 @@ __global__ __launch_bounds__(64) void sift_describe_kernel(const float* __restri
     if (lane == 0) {
         float* o = kp_out + (size_t)k * 4;
         o[0] = ldexpf(kp.x, kp.o - 1), o[1] = ldexpf(kp.y, kp.o - 1), o[2] = ldexpf(kp.scl, kp.o), o[3] = kp.resp;
+    }
+}
+
+// Test-facing (gtsfm_sift_math): one of the __device__ functions above, element-wise, one thread per element. in / out are 32-bit
+// words: floats, or int32 for SIFT_FN_REFLECT101.
+__global__ __launch_bounds__(256) void sift_math_kernel(int fn, const float* __restrict__ in, float* __restrict__ out, int n) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    switch (fn) {
+        case GTSFM_SIFT_FN_EXP2: out[i] = sift_exp2(in[i]); break;
+        case GTSFM_SIFT_FN_EXP: out[i] = sift_exp(in[i]); break;
+        case GTSFM_SIFT_FN_ATAN2_DEG: out[i] = sift_atan2_deg(in[2 * (size_t)i], in[2 * (size_t)i + 1]); break;
+        case GTSFM_SIFT_FN_SINCOS_DEG: {
+            float cs, sn;
+            sift_sincos_deg(in[i], &cs, &sn);
+            out[2 * (size_t)i] = cs, out[2 * (size_t)i + 1] = sn;
+            break;
+        }
+        case GTSFM_SIFT_FN_SOLVE3: {
+            const float* p = in + 12 * (size_t)i;
+            float A[3][3] = {{p[0], p[1], p[2]}, {p[3], p[4], p[5]}, {p[6], p[7], p[8]}};
+            float b[3] = {p[9], p[10], p[11]};
+            sift_solve3(A, b);
+            out[3 * (size_t)i] = b[0], out[3 * (size_t)i + 1] = b[1], out[3 * (size_t)i + 2] = b[2];
+            break;
+        }
+        case GTSFM_SIFT_FN_REFLECT101: {
+            const int* q = reinterpret_cast<const int*>(in) + 2 * (size_t)i;
+            const bool ok = q[1] >= 1 && q[1] <= (1 << 24) && q[0] >= -(1 << 24) && q[0] <= (1 << 24);  // what a blur can ask for
+            reinterpret_cast<int*>(out)[i] = ok ? sift_reflect101(q[0], q[1]) : -1;
+            break;
+        }
+        case GTSFM_SIFT_FN_PEAK_ANGLE: {
+            const float* p = in + 4 * (size_t)i;
+            out[i] = sift_peak_angle(__float_as_int(p[0]), p[1], p[2], p[3]);
+            break;
+        }
     }
 }
 
@@ -784,6 +828,16 @@ int gtsfm_sift_stage(const uint8_t* gray_dev, const uint8_t* mask_dev, int heigh
     GTSFM_CHECK_ARG(workspace_bytes >= s.total, "sift: workspace too small (%zu < %zu bytes)", workspace_bytes, s.total);
     return sift_image(gray_dev, mask_dev, height, width, g, s, stage, 0, cand_capacity, kp_capacity, out_dev, counts_dev, nullptr, nullptr,
                       reinterpret_cast<char*>(workspace_dev), (hipStream_t)stream);
+}
+
+int gtsfm_sift_math(int fn, const void* in_dev, void* out_dev, int n, void* stream) {
+    GTSFM_CHECK_ARG(in_dev && out_dev, "sift_math: null pointer");
+    GTSFM_CHECK_ARG(fn >= GTSFM_SIFT_FN_EXP2 && fn <= GTSFM_SIFT_FN_PEAK_ANGLE, "sift_math: unknown function %d", fn);
+    GTSFM_CHECK_ARG(n >= 1 && n <= (1 << 24), "sift_math: n must be in 1 .. 2^24 (got %d)", n);
+    hipLaunchKernelGGL(sift_math_kernel, dim3(ceil_div(n, 256)), dim3(256), 0, (hipStream_t)stream, fn, reinterpret_cast<const float*>(in_dev),
+                       reinterpret_cast<float*>(out_dev), n);
+    GTSFM_CHECK_LAUNCH("sift_math_kernel");
+    return GTSFM_OK;
 }
 
 }  // extern "C"

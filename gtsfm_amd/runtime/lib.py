@@ -240,6 +240,7 @@ SIGNATURES = {
         C.c_int,
         [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p],
     ),
+    "gtsfm_sift_math": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "gtsfm_tracks_workspace_bytes": (C.c_size_t, [C.c_longlong, C.c_longlong]),
     "gtsfm_tracks_from_matches": (
         C.c_int,

@@ -620,6 +620,25 @@ int gtsfm_sift_detect_and_describe(const uint8_t* gray_dev, const uint8_t* mask_
 int gtsfm_sift_stage(const uint8_t* gray_dev, const uint8_t* mask_dev, int height, int width, int stage, int cand_capacity, int kp_capacity, void* out_dev,
                      int32_t* counts_dev, void* workspace_dev, size_t workspace_bytes, void* stream);
 
+/* The explicit float32 functions behind the byte-identity contract, element-wise on n (1 .. 2^24) elements, for tests: one small
+ * kernel that calls the __device__ functions the pipeline calls; the call does not wait. All arrays hold 32-bit words.
+ *   EXP2, EXP     in [n] float t                      -> out [n] float
+ *   ATAN2_DEG     in [n][2] float y, x                -> out [n] float degrees in [0, 360]
+ *   SINCOS_DEG    in [n] float degrees                -> out [n][2] float cos, sin
+ *   SOLVE3        in [n][12] float A (row-major), b   -> out [n][3] float X with A X = b (a singular system gives 0)
+ *   REFLECT101    in [n][2] int32 index, length       -> out [n] int32 (-1 unless 1 <= length <= 2^24 and |index| <= 2^24)
+ *   PEAK_ANGLE    in [n][4] int32 bin j, float h[j - 1], h[j], h[j + 1] of the smoothed orientation histogram -> out [n] float degrees */
+enum {
+    GTSFM_SIFT_FN_EXP2 = 0,
+    GTSFM_SIFT_FN_EXP = 1,
+    GTSFM_SIFT_FN_ATAN2_DEG = 2,
+    GTSFM_SIFT_FN_SINCOS_DEG = 3,
+    GTSFM_SIFT_FN_SOLVE3 = 4,
+    GTSFM_SIFT_FN_REFLECT101 = 5,
+    GTSFM_SIFT_FN_PEAK_ANGLE = 6
+};
+int gtsfm_sift_math(int fn, const void* in_dev, void* out_dev, int n, void* stream);
+
 /* ------------------------------------------------------------------------------------------------------------
  * Feature tracks: union-find over verified matches
  *   replaces gtsfm/data_association/dsf_tracks_estimator.py:51-85, cpp_dsf_tracks_estimator.py:63-84 (gtsam's DSFMapIndexPair /

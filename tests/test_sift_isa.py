@@ -10,7 +10,7 @@ from conftest import REPO
 
 CSRC = REPO / "gtsfm_amd" / "csrc"
 KERNELS = ("sift_upsample_kernel", "sift_blur_row_kernel", "sift_blur_col_kernel", "sift_decimate_kernel", "sift_dog_kernel", "sift_extrema_kernel",
-           "sift_refine_kernel", "sift_orient_kernel", "sift_rank_kernel", "sift_describe_kernel")
+           "sift_refine_kernel", "sift_orient_kernel", "sift_rank_kernel", "sift_describe_kernel", "sift_math_kernel")
 
 
 @pytest.fixture(scope="module")
