@@ -221,6 +221,56 @@ class VerifiedScene:
             pruned, component = comp["pair_keep"].cpu().numpy(), comp["counts"]
         return ViewGraph(pairs, keep, pruned, results, component)
 
+    def rotation_averaging(self, edges: Optional[Iterable[Tuple[int, int]]] = None, averaging=None):
+        """Rotation averaging for the scene's edges (``gtsfm/multi_view_optimizer.py``: ``ShonanRotationAveraging.run_rotation_averaging``
+        between the view graph and 1DSfM) on the launches' rotations ``R`` where they lie. ``edges``: normally ``ViewGraph.edges`` (None:
+        every edge with a model); ``averaging``: a ``ShonanRotationAveraging`` (None: its defaults). The weight of an edge is the square of
+        the count of verified correspondences the launch holds on the device (``stats[:, 0]``: after ``two_view`` the count of the valid
+        mask), i.e. sigma = 1 / count as the reference weights by inliers; with ``weight_by_inliers`` off it is
+        ``1 / two_view_rotation_sigma^2``. Edges of ``extra`` take part with their uploaded rotations and the length of their host record.
+        No correspondence is downloaded: the rotations, the mask and the counters come back. On a status other than CONVERGED with weights
+        on, the solve is repeated unweighted and ``averaging`` is left unweighted, as the reference does after gtsam's RuntimeError
+        (``ShonanRotationAveraging.solve_with_retry``, the one place that rule lives); nothing else of ``averaging`` is changed.
+        Returns a ``RotationAverages``."""
+        from gtsfm_amd.averaging.rotation.shonan import RotationAverages, ShonanRotationAveraging
+        from gtsfm_amd.runtime.rotation_averaging_engine import COST_FIELDS, COUNTER_FIELDS
+        from gtsfm_amd.view_graph_estimator.cycle_consistent_rotation_estimator import rotation_matrix
+
+        averaging = averaging or ShonanRotationAveraging()
+        if self.feats is None:
+            return RotationAverages([], "NO_VALID_ROW", dict.fromkeys(COUNTER_FIELDS, 0), dict.fromkeys(COST_FIELDS, float("nan")), [], np.zeros(0), np.zeros(0, np.uint8))
+        import torch
+
+        device, num_images = self.feats["xy"].device, int(self.feats["xy"].shape[0])
+        engine = averaging.engine(device)
+        wanted = None if edges is None else {(int(a), int(b)) for a, b in edges}
+        pairs: List[Tuple[int, int]] = [(int(p[0]), int(p[1])) for v in self.launches for p in v["pairs"]]
+        rot = [v["R"].reshape(-1, 9).to(torch.float64) for v in self.launches]
+        count = [v["stats"][:, 0].to(torch.float64) for v in self.launches]
+        extra = [p for p in self.extra if p in self.verified and self.verified[p][0] is not None]
+        if extra:
+            pairs += [(int(p[0]), int(p[1])) for p in extra]
+            rot.append(torch.from_numpy(np.stack([rotation_matrix(self.verified[p][0]).reshape(9) for p in extra])).to(device))
+            count.append(torch.from_numpy(np.array([float(len(self.verified[p][2])) for p in extra])).to(device))
+        pair_images = torch.from_numpy(np.asarray(pairs, np.int32).reshape(-1, 2)).to(device)
+        rotation = torch.cat(rot).contiguous() if rot else torch.empty((0, 9), dtype=torch.float64, device=device)
+        counts = torch.cat(count).contiguous() if count else torch.empty(0, dtype=torch.float64, device=device)
+        on = (counts > 0).to(torch.uint8)
+        if wanted is not None and pairs:
+            on = (on * torch.from_numpy(np.array([p in wanted for p in pairs], np.uint8)).to(device)).contiguous()
+
+        def solve(weighted):
+            sigma = float(averaging._two_view_rotation_sigma)
+            weight = (counts * counts).contiguous() if weighted else torch.full_like(counts, 1.0 / (sigma * sigma))
+            out = engine.average(pair_images, rotation, weight, on, num_images=num_images, **averaging._solver_options)
+            return out["status"][0], (weight, out)
+
+        weight, out = averaging.solve_with_retry(solve)
+        wri, valid = out["wRi"][0].cpu().numpy(), out["node_valid"][0].cpu().numpy()
+        return RotationAverages([wri[i].reshape(3, 3).copy() if valid[i] else None for i in range(num_images)], out["status"][0],
+                                dict(zip(COUNTER_FIELDS, (int(x) for x in out["counters"][0]))), dict(zip(COST_FIELDS, (float(x) for x in out["costs"][0]))),
+                                pairs, weight.cpu().numpy(), on.cpu().numpy())
+
     def translation_inliers(self, wRi_list: List[Any], camera_intrinsics: List[Any], edges: Optional[Iterable[Tuple[int, int]]] = None, averaging=None):  # noqa: N803
         """1DSfM outlier rejection for the scene's edges (the first half of translation averaging, ``gtsfm/multi_view_optimizer.py:175-199``
         with ``averaging_1dsfm.py:234-315,530-549``) on the launches' unit translations ``t`` and the tracks of ``edges`` (normally

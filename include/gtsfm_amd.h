@@ -840,6 +840,54 @@ int gtsfm_translation_inliers_f64(const int32_t* pair_images_dev, const double* 
                                   double* meas_weight_dev, uint8_t* pair_inlier_dev, uint8_t* meas_inlier_dev, uint8_t* camera_inlier_dev,
                                   int32_t* position_dev, int32_t* counts_dev, void* stream);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * Rotation averaging (float64)
+ *   replaces gtsfm/averaging/rotation/shonan.py:122-168,185-204 (ShonanRotationAveraging._run_with_consecutive_ordering and
+ *   chordal_initialize: gtsam's InitializePose3::initializeOrientations and ShonanAveraging3 at p = 3), called from
+ *   gtsfm/multi_view_optimizer.py between the view graph and 1DSfM.
+ * A node is an image, R_k = wRk. A row is pair_images_dev [E][2] int32 = (i1, i2), rotation_dev [E][9] float64 = M = i2Ri1 row-major (what
+ * the verifier and gtsfm_two_view_ba_f64 write; the model is wRi1 = wRi2 . M), weight_dev [E] float64 = kappa = 1 / sigma^2, pair_enable_dev
+ * [E] uint8 optional (NULL: every row). Either orientation of a pair and the same pair several times are legal (priors are further rows).
+ * A row is VALID when it is enabled, its nine numbers and its weight are finite and kappa > 0. An enabled row with i1 == i2 or an index
+ * outside 0 .. num_images - 1 makes the call fail (GTSFM_ERR_INVALID, gtsfm_last_error) with no output written.
+ * The cost is f(R) = sum_e kappa_e |R_i2 M_e - R_i1|_F^2 over SO(3)^n: Shonan's chordal cost at p = 3 up to gtsam's factor 1/2. anchor = -1
+ * takes the i2 of the valid row with the smallest row index (measurements[0].key1()). Only the anchor's connected component over the valid
+ * rows is solved; every other image gets a NaN rotation and node_valid 0; the output gauge is R_anchor = I exactly.
+ * A. Chordal initialisation: min sum_e |X_i2 M_e - X_i1|_F^2 over 3 x 3 matrices, unweighted, X_anchor = I, by conjugate gradients from X = 0
+ * (one step length for the nine columns) to |r| <= chordal_tol |r0| or chordal_max_iterations; every X_k is projected onto SO(3) by a
+ * one-sided Jacobi SVD. B. Riemannian trust region with Steihaug-Toint truncated CG and the exact Hessian (as SE-Sync at fixed rank), the
+ * Cayley retraction, rho regularised as Manopt does; accept at rho > 0.1, Delta / 4 under 0.25, Delta * 2 above 0.75 on the boundary; the
+ * inner loop ends at |r| <= |r0| min(kappa_cg, |r0|^theta) (theta one of 0, 0.5, 1, 2: there is no libm call in the stage), on the boundary,
+ * on negative curvature or after max_inner steps (0: three per node); the outer loop ends at |g|_inf <= gradient_tol * max kappa or after
+ * max_outer iterations. Sums run over a node's rows in ascending (neighbour, row) order and over the nodes by a fixed pairwise tree, so
+ * every byte is fixed by the inputs: not by the lane count, the run, or the problem's place in a batch. The specification is
+ * tests/rotation_averaging_reference.py, operation for operation.
+ * Batch: problem_row_off_dev [P + 1] int64 (NULL with num_problems 1: one problem over every row) gives each problem a row range of the same
+ * arrays; one workgroup solves one problem. Offsets not ascending within 0 .. num_rows are refused like a bad row.
+ * PARITY UNPINNED towards the reference (nothing of gtsam was observed running): its Levenberg-Marquardt path, the soft anchor and the
+ * Karcher / gauge terms, Rot3::ClosestTo in the last bits, its output gauge. NOT DONE HERE: Shonan's optimality certificate and the rank
+ * staircase p > 3 -- the point returned is a critical point reached from the chordal start, which on graphs with outliers may not be the
+ * global minimum (tests/rotation_averaging_scenes.py holds one such scene); Huber weighting; the random start.
+ * ---------------------------------------------------------------------------------------------------------- */
+
+/* Bytes of device workspace (0 for sizes out of range: negative, 2^28 rows, 2^24 images, 2^28 images over all problems): 33 per row and about
+ * 570 per image and problem. One workgroup solves one problem, start to end: a node's list is ranked in O(degree^2) and every pass walks
+ * the lists with 256 lanes, so a call's time grows with rows x steps on ONE CU (163 ms at 48 725 rows and 1000 images, measured). The size
+ * limits above are those of the index arithmetic, not a promise of speed: beyond about 10^5 rows or a degree of a few thousand split the
+ * graph into problems (clusters) of a batch. */
+size_t gtsfm_rotation_averaging_workspace_bytes(long long num_rows, long long num_images, long long num_problems);
+
+/* Outputs per problem: rotation_out_dev [P][num_images][9] wRi (NaN outside the component), node_valid_dev [P][num_images] uint8,
+ * counters_dev [P][8] int32 = status (0 CONVERGED, 1 MAX_ITERATIONS, 2 NO_VALID_ROW: all outputs NaN / 0, 3 NON_FINITE: a NaN met inside,
+ * outputs NaN, mask 0), outer iterations, accepted steps, Hessian applications, chordal CG steps, component size, anchor, valid rows;
+ * costs_dev [P][4] float64 = the cost with every rotation the identity, after the chordal initialisation, at the end, and the final
+ * |g|_inf. The call waits for the stream once, for the two refusal flags; the inputs are not changed. */
+int gtsfm_rotation_averaging_f64(const int32_t* pair_images_dev, const double* rotation_dev, const double* weight_dev, const uint8_t* pair_enable_dev,
+                                 long long num_rows, int num_images, const long long* problem_row_off_dev, int num_problems, int anchor,
+                                 double chordal_tol, int chordal_max_iterations, double delta0, double kappa_cg, double theta, double gradient_tol,
+                                 int max_outer, int max_inner, void* workspace_dev, size_t workspace_bytes, double* rotation_out_dev,
+                                 uint8_t* node_valid_dev, int32_t* counters_dev, double* costs_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

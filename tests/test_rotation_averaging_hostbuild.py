@@ -1,0 +1,102 @@
+"""CPU: the rotation-averaging solver itself (ra_validate and ra_solve of gtsfm_amd/csrc/rotation_averaging_kernels.hip, the functions the kernels
+run), compiled for the host into the stand-alone program tools/rotation_averaging_host_main.cpp -- once plain and once with the host's address
+and undefined-behaviour sanitizers -- on every scene of tests/rotation_averaging_scenes.py. The program solves each scene with one lane over
+zeroed memory and with the device's 256-lane partition, last lane first, over memory filled with 0xFF, and every problem of a batch alone as
+well; all must be byte-equal to each other and to the restatement (tests/rotation_averaging_reference.py): rotations, mask, counters and
+costs. The program runs as its own process; no sanitizer is loaded into Python and no GPU is involved."""
+
+import os
+import shutil
+import struct
+import subprocess
+
+import numpy as np
+import pytest
+
+from gtsfm_amd.csrc.build import ARCH, HIPCC
+from tests import rotation_averaging_reference as ref
+from tests import rotation_averaging_scenes as scenes
+from tests.conftest import REPO
+
+pytestmark = pytest.mark.skipif(shutil.which(HIPCC) is None, reason="hipcc is not installed")
+
+SOURCE = REPO / "tools" / "rotation_averaging_host_main.cpp"
+FLAGS = [f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-ffp-contract=off", "-Wall", "-Wno-unused-function"]  # gtsfm_amd/csrc/build.py's
+SANITIZE = "-fsanitize=address,undefined"
+MAGIC = 0x3147564154524D46
+
+
+@pytest.fixture(scope="module", params=["plain", "sanitized"])
+def program(request, tmp_path_factory):
+    d = tmp_path_factory.mktemp(f"rotation_averaging_host_{request.param}")
+    san = request.param == "sanitized"
+    obj, exe = d / "main.o", d / "rotation_averaging_host"
+    # the device side ignores the host-only flag; the link step takes it plain
+    subprocess.run([HIPCC, *FLAGS, *(["-Xarch_host", SANITIZE] if san else []), "-c", str(SOURCE), "-o", str(obj)], check=True, capture_output=True, timeout=600)
+    subprocess.run([HIPCC, *([SANITIZE] if san else []), str(obj), "-o", str(exe)], check=True, capture_output=True, timeout=600)
+    return exe, d
+
+
+def write_scene(path, pair_images, rotation, weight, pair_enable, num_images, row_off, anchor, opts):
+    e, p = len(pair_images), len(row_off) - 1
+    with open(path, "wb") as f:
+        f.write(struct.pack("<16q", MAGIC, e, num_images, p, 0 if pair_enable is None else 1, anchor, opts["chordal_max_iterations"], opts["max_outer"], opts["max_inner"], *[0] * 7))
+        f.write(struct.pack("<8d", opts["chordal_tol"], opts["delta0"], opts["kappa_cg"], opts["theta"], opts["gradient_tol"], 0.0, 0.0, 0.0))
+        for a, dt in ((pair_images, np.int32), (rotation, np.float64), (weight, np.float64), (np.ones(e) if pair_enable is None else pair_enable, np.uint8), (row_off, np.int64)):
+            f.write(np.ascontiguousarray(a, dt).tobytes())
+
+
+def run_program(program, pair_images, rotation, weight, pair_enable, num_images, row_off, anchor, opts, expect_status=0):
+    exe, d = program
+    path, out_path = d / "scene.bin", d / "out.bin"
+    write_scene(path, pair_images, rotation, weight, pair_enable, num_images, row_off, anchor, opts)
+    out_path.unlink(missing_ok=True)
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0", UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1")
+    done = subprocess.run([str(exe), str(path), str(out_path)], capture_output=True, text=True, timeout=600, env=env)
+    assert done.returncode == expect_status, f"exit status {done.returncode}\n{done.stderr[-3000:]}"
+    assert "runtime error" not in done.stderr and "Sanitizer" not in done.stderr, done.stderr[-3000:]
+    if expect_status:
+        return done.stderr
+    raw, p, n = out_path.read_bytes(), len(row_off) - 1, num_images
+    out, at = {}, 0
+    for key, dt, shape in (("wRi", np.float64, (p, n, 9)), ("node_valid", np.uint8, (p, n)), ("counters", np.int32, (p, 8)), ("costs", np.float64, (p, 4))):
+        count = int(np.prod(shape))
+        out[key] = np.frombuffer(raw, dtype=dt, count=count, offset=at).reshape(shape)
+        at += count * np.dtype(dt).itemsize
+    assert at == len(raw)
+    return out
+
+
+def assert_equals_restatement(out, p, want, what):
+    assert out["wRi"][p].tobytes() == want["wRi"].tobytes(), f"{what}: rotations"
+    assert out["node_valid"][p].tobytes() == want["node_valid"].tobytes(), f"{what}: node_valid"
+    assert out["counters"][p].tolist() == [want["counters"][k] for k in ref.COUNTER_FIELDS], f"{what}: counters"
+    assert out["costs"][p].tobytes() == np.array([want["costs"][k] for k in ref.COST_FIELDS]).tobytes(), f"{what}: costs"
+
+
+@pytest.mark.parametrize("name", scenes.SCENE_NAMES)
+def test_host_build_equals_the_restatement(program, name):
+    sc = scenes.get(name)
+    out = run_program(program, sc["pair_images"], sc["rotation"], sc["weight"], sc["pair_enable"], sc["num_images"], [0, len(sc["pair_images"])], sc["anchor"], scenes.options_of(sc))
+    assert_equals_restatement(out, 0, scenes.expected(name), name)
+
+
+def test_host_build_batch(program):
+    """Three problems over row ranges of the same arrays: each equals the restatement of its own rows (and the program itself holds each to its solo run)."""
+    parts = [scenes.get(n) for n in ("ring65", "gaps", "duplicate_pairs")]
+    n = max(x["num_images"] for x in parts)
+    pair_images = np.concatenate([x["pair_images"] for x in parts])
+    rotation, weight = np.concatenate([x["rotation"] for x in parts]), np.concatenate([x["weight"] for x in parts])
+    row_off = np.concatenate([[0], np.cumsum([len(x["pair_images"]) for x in parts])]).tolist()
+    out = run_program(program, pair_images, rotation, weight, None, n, row_off, -1, dict(ref.DEFAULTS))
+    for p, (lo, hi) in enumerate(zip(row_off[:-1], row_off[1:])):
+        want = ref.solve(pair_images[lo:hi], rotation[lo:hi], weight[lo:hi], num_images=n)
+        assert_equals_restatement(out, p, want, f"problem {p}")
+
+
+@pytest.mark.parametrize("case", ["self_pair", "out_of_range", "negative", "offsets"])
+def test_host_build_refuses_bad_input(program, case):
+    pairs = {"self_pair": [(0, 1), (2, 2)], "out_of_range": [(0, 1), (1, 5)], "negative": [(-1, 1), (1, 2)]}.get(case, [(0, 1), (1, 2)])
+    row_off = [0, 3] if case == "offsets" else [0, 2]
+    err = run_program(program, np.asarray(pairs, np.int32), np.tile(np.eye(3).reshape(9), (2, 1)), np.ones(2), None, 3, row_off, -1, dict(ref.DEFAULTS), expect_status=3)
+    assert "refused" in err
