@@ -39,6 +39,18 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 __host__ __device__ static inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
 static inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
+// Lays a workspace out: consecutive pieces, each starting at a multiple of 256 bytes from `base`. A size query passes a null base and
+// reads `used`.
+struct WorkspaceCarver {
+    void* base;
+    size_t used;
+    void* take(size_t bytes) {
+        const size_t at = used;
+        used += align_up(bytes, 256);
+        return (void*)((uintptr_t)base + at);
+    }
+};
+
 // Wave-wide reductions over all 64 lanes (result valid in every lane).
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll

@@ -22,7 +22,7 @@
 #include <math.h>
 
 #include "../../include/gtsfm_amd.h"
-#include "common.h"
+#include "graph_prims.h"
 
 #define RA_HD __host__ __device__ __forceinline__
 #define RA_THREADS 256
@@ -64,16 +64,6 @@ static RaHostLanes ra_host = {1, 0};
 
 namespace {
 
-RA_HD int ra_atomic_add(int* p, int v) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    return atomicAdd(p, v);
-#else
-    const int old = *p;
-    *p = old + v;
-    return old;
-#endif
-}
-
 struct RaWorkspace {
     int* flags;         // [RA_FLAG_WORDS]
     uint8_t* valid;     // [E]
@@ -87,27 +77,22 @@ struct RaWorkspace {
 
 RaWorkspace ra_layout(void* base, long long rows, long long images, long long problems) {
     RaWorkspace w;
-    size_t used = 0;
+    WorkspaceCarver ws{base, 0};
     const size_t e = (size_t)rows, n = (size_t)images, p = (size_t)problems;
-    auto take = [&](size_t bytes) {
-        const size_t at = used;
-        used += align_up(bytes, 256);
-        return (void*)((uintptr_t)base + at);
-    };
-    w.flags = (int*)take(RA_FLAG_WORDS * 4);
-    w.valid = (uint8_t*)take(e);
-    w.off = (int*)take(p * (n + 2) * 4);
-    w.cid = (int*)take(p * (n + 2) * 4);
-    w.cursor = (int*)take(p * n * 4);
-    w.reach = (int*)take(p * n * 4);
-    w.cnode = (int*)take(p * n * 4);
-    w.lanebuf = (long long*)take(p * RA_THREADS * 8);
-    w.raw_row = (int*)take(2 * e * 4);
-    w.raw_owner = (int*)take(2 * e * 4);
-    w.adj_nbr = (int*)take(2 * e * 4);
-    w.adj_row = (int*)take(2 * e * 4);
-    w.state = (double*)take(p * RA_NODE_DOUBLES * (n ? n : 1) * 8);
-    w.bytes = used;
+    w.flags = (int*)ws.take(RA_FLAG_WORDS * 4);
+    w.valid = (uint8_t*)ws.take(e);
+    w.off = (int*)ws.take(p * (n + 2) * 4);
+    w.cid = (int*)ws.take(p * (n + 2) * 4);
+    w.cursor = (int*)ws.take(p * n * 4);
+    w.reach = (int*)ws.take(p * n * 4);
+    w.cnode = (int*)ws.take(p * n * 4);
+    w.lanebuf = (long long*)ws.take(p * RA_THREADS * 8);
+    w.raw_row = (int*)ws.take(2 * e * 4);
+    w.raw_owner = (int*)ws.take(2 * e * 4);
+    w.adj_nbr = (int*)ws.take(2 * e * 4);
+    w.adj_row = (int*)ws.take(2 * e * 4);
+    w.state = (double*)ws.take(p * RA_NODE_DOUBLES * (n ? n : 1) * 8);
+    w.bytes = ws.used;
     return w;
 }
 
@@ -423,8 +408,8 @@ RA_HD void ra_solve(const RaArgs& a, int p) {
     long long first = q.hi;
     for (long long m = q.lo + lane; m < q.hi; m += lanes) {
         if (!a.w.valid[m]) continue;
-        ra_atomic_add(&q.off[a.pair_images[2 * m]], 1);
-        ra_atomic_add(&q.off[a.pair_images[2 * m + 1]], 1);
+        hd_atomic_add(&q.off[a.pair_images[2 * m]], 1);
+        hd_atomic_add(&q.off[a.pair_images[2 * m + 1]], 1);
         if (m < first) first = m;
     }
     q.lanebuf[lane] = first;
@@ -452,7 +437,7 @@ RA_HD void ra_solve(const RaArgs& a, int p) {
     for (long long m = q.lo + lane; m < q.hi; m += lanes) {
         if (!a.w.valid[m]) continue;
         const int i1 = a.pair_images[2 * m], i2 = a.pair_images[2 * m + 1];
-        const int s1 = q.off[i1] + ra_atomic_add(&q.cursor[i1], 1), s2 = q.off[i2] + ra_atomic_add(&q.cursor[i2], 1);
+        const int s1 = q.off[i1] + hd_atomic_add(&q.cursor[i1], 1), s2 = q.off[i2] + hd_atomic_add(&q.cursor[i2], 1);
         if (s1 < q.off[i1 + 1]) q.raw_row[s1] = (int)(m - q.lo), q.raw_owner[s1] = i1;  // always true: exactly degree rows ask
         if (s2 < q.off[i2 + 1]) q.raw_row[s2] = (int)(m - q.lo), q.raw_owner[s2] = i2;
     }

@@ -4,28 +4,8 @@
 // holds two keypoints of one image. The result is a set partition, so everything here is integer and every output byte is fixed by the
 // input's edge SET: not by the order of pairs or rows, not by the grid, not by timing.
 //
-// LABELLING. label[] is a snapshot that a launch only reads, parent[] is the forest the same launch hooks into.
-//   init     : parent[v] = label[v] = v, marks / counters / flags cleared.
-//   hook     : per active edge (u, v): ru = label[u], rv = label[v] (the roots as of the last launch boundary); when they differ,
-//              atomicMin(&parent[max(ru, rv)], min(ru, rv)) and the round's flag is raised. The first round also marks both ends as
-//              touched. After the launch parent[x] = min(x, every root hooked onto x): a minimum, whatever the order.
-//   compress : thread v chases parent[] from v to its root and stores label[v] = parent[v] = root. Only thread v stores parent[v] or
-//              label[v] in this launch; a chase that passes through w reads parent[w] before or after thread w's store, and both
-//              values lie on w's path to the same root.
-//   The host reads the round's 4-byte flag after the compress launch. A round that raised no flag found label[u] == label[v] for every
-//   active edge in data published by a launch boundary, so every component carries one label, and since parent[x] <= x that label is
-//   the component's smallest node. The host stops there, or fails at TRK_MAX_ROUNDS without writing a result.
-//
-// Invariants:
-//   1. parent[x] <= x in every snapshot any thread can observe, fresh or stale: a chase strictly decreases and ends at an x with
-//      parent[x] == x.
-//   2. Labels only decrease: parent[x] changes by atomicMin, or by thread x storing its own root, which is <= parent[x].
-//   3. No kernel waits for another workgroup of its own launch: no spin loop, no decoupled look-back, no flag polled across workgroups.
-//      What a later step needs from all workgroups, it gets from a launch boundary.
-//   4. The only cross-workgroup traffic inside a launch is the return value of an atomic (the gather cursor). The eight XCD L2s are not
-//      coherent with each other and a CU's L1 is never refreshed by another CU's stores, so no kernel reads with a plain load what
-//      another workgroup of the same launch stores, except the chase of `compress`, for which invariant 1 makes any mix of old and new
-//      values correct.
+// LABELLING. The union-find rounds of graph_prims.h (its header comment states the algorithm and its four invariants): trk_hook_kernel decodes
+// a match row into its two nodes and calls uf_hook, trk_compress_kernel calls uf_compress, and uf_run_rounds owns the host's loop.
 //
 // ASSEMBLY (after the fixed point; every step is a launch of its own).
 //   count    : atomicAdd(&cnt[label[v]], 1) per touched node: integer adds, any order.
@@ -41,14 +21,12 @@
 //   write    : measurement moff[root] + rank <- (image, keypoint, xy); the root writes track_off; one thread the counts.
 
 #include "../../include/gtsfm_amd.h"
-#include "common.h"
+#include "graph_prims.h"
 
 #define TRK_THREADS 256
 #define TRK_SCAN_ITEMS 4                                // values per thread of a scan block
 #define TRK_SCAN_BLOCK (TRK_THREADS * TRK_SCAN_ITEMS)   // values per scan block
-#define TRK_MAX_ROUNDS 64
 #define TRK_MAX_BLOCKS (1 << 20)                        // grid of the edge kernel; more rows loop inside the kernel
-#define TRK_FLAG_WORDS (8 + TRK_MAX_ROUNDS)             // word 0: bad input; word 8 + r: round r hooked something
 
 typedef unsigned long long trk_u64;  // a scan value: (count << 32) | length, both below 2^31 in total, so the halves never carry
 
@@ -63,27 +41,22 @@ struct TrkWorkspace {
 // the one place that lays the workspace out (the size query passes a null base)
 TrkWorkspace trk_layout(void* base, long long num_nodes) {
     TrkWorkspace w;
-    size_t used = 0;
+    WorkspaceCarver ws{base, 0};
     const size_t n = (size_t)num_nodes;
-    auto take = [&](size_t bytes) {
-        const size_t at = used;
-        used += align_up(bytes, 256);
-        return (void*)((uintptr_t)base + at);
-    };
-    w.parent = (int*)take(n * 4);
-    w.label = (int*)take(n * 4);
-    w.mark = (int*)take(n * 4);
-    w.cnt = (int*)take(n * 4);
-    w.cursor = (int*)take(n * 4);
-    w.members = (int*)take(n * 4);
-    w.rank = (int*)take(n * 4);
-    w.invalid = (int*)take(n * 4);
-    w.seg = (trk_u64*)take(n * 8);
-    w.out = (trk_u64*)take(n * 8);
-    w.seg_sums = (trk_u64*)take(((n + TRK_SCAN_BLOCK - 1) / TRK_SCAN_BLOCK + 1) * 8);
-    w.out_sums = (trk_u64*)take(((n + TRK_SCAN_BLOCK - 1) / TRK_SCAN_BLOCK + 1) * 8);
-    w.flags = (int*)take(TRK_FLAG_WORDS * 4);
-    w.bytes = used;
+    w.parent = (int*)ws.take(n * 4);
+    w.label = (int*)ws.take(n * 4);
+    w.mark = (int*)ws.take(n * 4);
+    w.cnt = (int*)ws.take(n * 4);
+    w.cursor = (int*)ws.take(n * 4);
+    w.members = (int*)ws.take(n * 4);
+    w.rank = (int*)ws.take(n * 4);
+    w.invalid = (int*)ws.take(n * 4);
+    w.seg = (trk_u64*)ws.take(n * 8);
+    w.out = (trk_u64*)ws.take(n * 8);
+    w.seg_sums = (trk_u64*)ws.take(((n + TRK_SCAN_BLOCK - 1) / TRK_SCAN_BLOCK + 1) * 8);
+    w.out_sums = (trk_u64*)ws.take(((n + TRK_SCAN_BLOCK - 1) / TRK_SCAN_BLOCK + 1) * 8);
+    w.flags = (int*)ws.take(UF_FLAG_WORDS * 4);
+    w.bytes = ws.used;
     return w;
 }
 
@@ -101,7 +74,7 @@ __global__ __launch_bounds__(TRK_THREADS) void trk_init_kernel(int* __restrict__
                                                                int* __restrict__ cnt, int* __restrict__ cursor, int* __restrict__ invalid,
                                                                int* __restrict__ flags, long long num_nodes) {
     const long long v = (long long)blockIdx.x * TRK_THREADS + threadIdx.x;
-    if (v < TRK_FLAG_WORDS) flags[v] = 0;
+    if (v < UF_FLAG_WORDS) flags[v] = 0;
     if (v >= num_nodes) return;
     parent[v] = (int)v;
     label[v] = (int)v;
@@ -144,25 +117,14 @@ __global__ __launch_bounds__(TRK_THREADS) void trk_hook_kernel(const int* __rest
             flags[0] = 1;
             continue;
         }
-        if (round == 0) {
-            mark[u] = 1;
-            mark[v] = 1;
-        }
-        const int ru = label[u], rv = label[v];
-        if (ru != rv) {
-            atomicMin(&parent[ru > rv ? ru : rv], ru < rv ? ru : rv);
-            flags[8 + round] = 1;
-        }
+        uf_hook(parent, label, mark, flags, u, v, round);
     }
 }
 
 __global__ __launch_bounds__(TRK_THREADS) void trk_compress_kernel(int* parent, int* __restrict__ label, long long num_nodes) {
     const long long v = (long long)blockIdx.x * TRK_THREADS + threadIdx.x;
     if (v >= num_nodes) return;
-    int x = parent[v];
-    for (int p = parent[x]; p != x; p = parent[x]) x = p;  // strictly decreasing (invariant 1)
-    label[v] = x;
-    parent[v] = x;
+    uf_compress(parent, label, v);
 }
 
 __global__ __launch_bounds__(TRK_THREADS) void trk_count_kernel(const int* __restrict__ label, const int* __restrict__ mark, int* cnt,
@@ -260,23 +222,6 @@ __global__ __launch_bounds__(TRK_THREADS) void trk_write_kernel(const int* __res
 
 // ---- exclusive prefix sums of trk_u64 values: block sums, a scan of the sums by one workgroup, then an add ----
 
-// exclusive scan of one value per thread over the workgroup; *total receives the workgroup's sum
-__device__ __forceinline__ trk_u64 trk_block_exclusive(trk_u64 x, trk_u64* lds /*[TRK_THREADS]*/, trk_u64* total) {
-    const int tid = threadIdx.x;
-    lds[tid] = x;
-    __syncthreads();
-    for (int off = 1; off < TRK_THREADS; off <<= 1) {
-        const trk_u64 add = tid >= off ? lds[tid - off] : 0;
-        __syncthreads();
-        lds[tid] += add;
-        __syncthreads();
-    }
-    const trk_u64 incl = lds[tid];
-    *total = lds[TRK_THREADS - 1];
-    __syncthreads();  // lds may be reused
-    return incl - x;
-}
-
 __global__ __launch_bounds__(TRK_THREADS) void trk_scan_reduce_kernel(const trk_u64* __restrict__ val, long long n, trk_u64* __restrict__ sums) {
     __shared__ trk_u64 lds[TRK_THREADS];
     const long long base = (long long)blockIdx.x * TRK_SCAN_BLOCK + (long long)threadIdx.x * TRK_SCAN_ITEMS;
@@ -284,7 +229,7 @@ __global__ __launch_bounds__(TRK_THREADS) void trk_scan_reduce_kernel(const trk_
 #pragma unroll
     for (int k = 0; k < TRK_SCAN_ITEMS; ++k) s += base + k < n ? val[base + k] : 0;
     trk_u64 total;
-    trk_block_exclusive(s, lds, &total);
+    block_exclusive_scan<TRK_THREADS>(s, lds, &total);
     if (threadIdx.x == 0) sums[blockIdx.x] = total;
 }
 
@@ -296,7 +241,7 @@ __global__ __launch_bounds__(TRK_THREADS) void trk_scan_sums_kernel(trk_u64* sum
         const long long i = base + threadIdx.x;
         const trk_u64 x = i < m ? sums[i] : 0;
         trk_u64 total;
-        const trk_u64 excl = trk_block_exclusive(x, lds, &total);
+        const trk_u64 excl = block_exclusive_scan<TRK_THREADS>(x, lds, &total);
         if (i < m) sums[i] = carry + excl;
         carry += total;
     }
@@ -313,7 +258,7 @@ __global__ __launch_bounds__(TRK_THREADS) void trk_scan_apply_kernel(trk_u64* va
         s += x[k];
     }
     trk_u64 total;
-    trk_u64 run = sums[blockIdx.x] + trk_block_exclusive(s, lds, &total);
+    trk_u64 run = sums[blockIdx.x] + block_exclusive_scan<TRK_THREADS>(s, lds, &total);
 #pragma unroll
     for (int k = 0; k < TRK_SCAN_ITEMS; ++k) {
         if (base + k < n) val[base + k] = run;
@@ -379,37 +324,35 @@ extern "C" int gtsfm_tracks_from_matches(const int32_t* match_idx_dev, const lon
     }
 
     const dim3 threads(TRK_THREADS);
-    const long long want_blocks = (num_nodes > TRK_FLAG_WORDS ? num_nodes : TRK_FLAG_WORDS) + TRK_THREADS - 1;
+    const long long want_blocks = (num_nodes > UF_FLAG_WORDS ? num_nodes : UF_FLAG_WORDS) + TRK_THREADS - 1;
     const dim3 node_grid((unsigned)(want_blocks / TRK_THREADS));
     const long long edge_blocks = (total_matches + TRK_THREADS - 1) / TRK_THREADS;
     const dim3 edge_grid((unsigned)(edge_blocks < TRK_MAX_BLOCKS ? edge_blocks : TRK_MAX_BLOCKS));
 
     hipLaunchKernelGGL(trk_init_kernel, node_grid, threads, 0, stream, w.parent, w.label, w.mark, w.cnt, w.cursor, w.invalid, w.flags, num_nodes);
     GTSFM_CHECK_LAUNCH("trk_init_kernel");
-    int rounds = 0;
-    for (;;) {
-        if (rounds == TRK_MAX_ROUNDS) {
-            gtsfm_set_error("gtsfm_tracks_from_matches: no fixed point after %d rounds (%lld nodes, %lld match rows, %d pairs); nothing was written",
-                            rounds, num_nodes, total_matches, num_pairs);
-            return GTSFM_ERR_INVALID;
-        }
+    const auto hook = [&](int round) -> int {
         hipLaunchKernelGGL(trk_hook_kernel, edge_grid, threads, 0, stream, match_idx_dev, match_off_dev, match_count_dev, inlier_mask_dev, pair_enable_dev,
-                           pair_images_dev, num_pairs, total_matches, node_off_dev, num_images, num_nodes, w.label, w.parent, w.mark, w.flags, rounds);
+                           pair_images_dev, num_pairs, total_matches, node_off_dev, num_images, num_nodes, w.label, w.parent, w.mark, w.flags, round);
         GTSFM_CHECK_LAUNCH("trk_hook_kernel");
+        return GTSFM_OK;
+    };
+    const auto compress = [&]() -> int {
         hipLaunchKernelGGL(trk_compress_kernel, node_grid, threads, 0, stream, w.parent, w.label, num_nodes);
         GTSFM_CHECK_LAUNCH("trk_compress_kernel");
-        int flag[2] = {0, 0};  // bad input, this round hooked
-        if (hipMemcpyAsync(&flag[0], w.flags, sizeof(int), hipMemcpyDeviceToHost, stream) != hipSuccess ||
-            hipMemcpyAsync(&flag[1], w.flags + 8 + rounds, sizeof(int), hipMemcpyDeviceToHost, stream) != hipSuccess ||
-            hipStreamSynchronize(stream) != hipSuccess) {
-            gtsfm_set_error("gtsfm_tracks_from_matches: round %d failed: %s", rounds, hipGetErrorString(hipGetLastError()));
-            return GTSFM_ERR_HIP;
-        }
-        GTSFM_CHECK_ARG(!flag[0], "gtsfm_tracks_from_matches: an active match row names an image outside 0 .. %d or a keypoint outside its image's table; nothing was written",
-                        num_images - 1);
-        ++rounds;
-        if (!flag[1]) break;
+        return GTSFM_OK;
+    };
+    int rounds = 0;
+    const UfOutcome labelled = uf_run_rounds(w.flags, stream, hook, compress, &rounds);
+    if (labelled == UF_LAUNCH_FAILED) return GTSFM_ERR_HIP;
+    if (labelled == UF_READ_FAILED) {
+        gtsfm_set_error("gtsfm_tracks_from_matches: round %d failed: %s", rounds, hipGetErrorString(hipGetLastError()));
+        return GTSFM_ERR_HIP;
     }
+    GTSFM_CHECK_ARG(labelled != UF_NO_FIXED_POINT, "gtsfm_tracks_from_matches: no fixed point after %d rounds (%lld nodes, %lld match rows, %d pairs); nothing was written",
+                    rounds, num_nodes, total_matches, num_pairs);
+    GTSFM_CHECK_ARG(labelled != UF_BAD_INPUT, "gtsfm_tracks_from_matches: an active match row names an image outside 0 .. %d or a keypoint outside its image's table; nothing was written",
+                    num_images - 1);
 
     hipLaunchKernelGGL(trk_count_kernel, node_grid, threads, 0, stream, w.label, w.mark, w.cnt, num_nodes);
     GTSFM_CHECK_LAUNCH("trk_count_kernel");

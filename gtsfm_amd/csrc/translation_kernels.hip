@@ -21,20 +21,16 @@
 //   phase 4  aggregate  : one lane per row walks the directions in order, recomputes |w| by the same instruction sequence, reads the two
 //            positions, adds and thresholds; inlier pairs mark their cameras (plain stores of 1), then a measurement stays an inlier only
 //            when its camera is marked. The intermediate is D x G int32, not D x rows float64.
-// Every per-index step is a TR_HD function that the kernels call with their global index and tools/translation_inliers_host_main.cpp calls
+// Every per-index step is a GTSFM_HD function that the kernels call with their global index and tools/translation_inliers_host_main.cpp calls
 // in another order and lane partition on a CPU; the atomics become plain updates there.
 
 #include <math.h>
 
 #include "../../include/gtsfm_amd.h"
-#include "common.h"
+#include "graph_prims.h"
 
-#define TR_HD __host__ __device__ __forceinline__
 #define TR_THREADS 256
 #define TR_WAVE 64
-#define TR_SCAN_THREADS 1024
-#define TR_SCAN_ITEMS 4
-#define TR_SCAN_BLOCK (TR_SCAN_THREADS * TR_SCAN_ITEMS)
 #define TR_MAX_ROWS (1ll << 28)
 #define TR_MAX_NODES (1ll << 28)
 #define TR_MAX_DIRECTIONS (1ll << 20)
@@ -46,25 +42,6 @@
 
 namespace {
 
-TR_HD int tr_atomic_add(int* p, int v) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    return atomicAdd(p, v);
-#else
-    const int old = *p;
-    *p = old + v;
-    return old;
-#endif
-}
-TR_HD long long tr_atomic_add64(long long* p, long long v) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    return (long long)atomicAdd((unsigned long long*)p, (unsigned long long)v);
-#else
-    const long long old = *p;
-    *p = old + v;
-    return old;
-#endif
-}
-
 struct TrWorkspace {
     long long *row_off, *cid, *coff;  // [NT + 1] degrees then list offsets by node id; [NT + 1] has-an-edge then compact ids; [cap + 1] compact offsets
     int *cursor, *key1, *key2, *raw_edge, *raw_owner, *adj_nbr, *adj_edge, *flags, *pos;
@@ -72,32 +49,27 @@ struct TrWorkspace {
     size_t bytes;
 };
 
-TR_HD long long tr_groups(long long num_directions) { return num_directions < TR_MAX_GROUPS ? (num_directions > 0 ? num_directions : 1) : TR_MAX_GROUPS; }
-TR_HD long long tr_lds_limit(int lds_node_limit) { return lds_node_limit < 0 || lds_node_limit > TR_LDS_NODES ? TR_LDS_NODES : lds_node_limit; }
+GTSFM_HD long long tr_groups(long long num_directions) { return num_directions < TR_MAX_GROUPS ? (num_directions > 0 ? num_directions : 1) : TR_MAX_GROUPS; }
+GTSFM_HD long long tr_lds_limit(int lds_node_limit) { return lds_node_limit < 0 || lds_node_limit > TR_LDS_NODES ? TR_LDS_NODES : lds_node_limit; }
 
 TrWorkspace tr_layout(void* base, long long rows, long long nodes, long long num_directions, long long node_capacity, int lds_node_limit) {
     TrWorkspace w;
-    size_t used = 0;
+    WorkspaceCarver ws{base, 0};
     const size_t m = (size_t)rows, nt = (size_t)nodes, cap = (size_t)node_capacity, d = (size_t)(num_directions > 0 ? num_directions : 0);
-    auto take = [&](size_t bytes) {
-        const size_t at = used;
-        used += align_up(bytes, 256);
-        return (void*)((uintptr_t)base + at);
-    };
-    w.row_off = (long long*)take((nt + 1) * 8);
-    w.cid = (long long*)take((nt + 1) * 8);
-    w.coff = (long long*)take((cap + 1) * 8);
-    w.cursor = (int*)take(nt * 4);
-    w.key1 = (int*)take(m * 4);
-    w.key2 = (int*)take(m * 4);
-    w.raw_edge = (int*)take(2 * m * 4);
-    w.raw_owner = (int*)take(2 * m * 4);
-    w.adj_nbr = (int*)take(2 * m * 4);
-    w.adj_edge = (int*)take(2 * m * 4);
-    w.flags = (int*)take(TR_FLAG_WORDS * 4);
-    w.pos = (int*)take(d * cap * 4);
-    w.state = (double*)take((long long)cap > tr_lds_limit(lds_node_limit) ? (size_t)tr_groups(num_directions) * 3 * cap * 8 : 0);
-    w.bytes = used;
+    w.row_off = (long long*)ws.take((nt + 1) * 8);
+    w.cid = (long long*)ws.take((nt + 1) * 8);
+    w.coff = (long long*)ws.take((cap + 1) * 8);
+    w.cursor = (int*)ws.take(nt * 4);
+    w.key1 = (int*)ws.take(m * 4);
+    w.key2 = (int*)ws.take(m * 4);
+    w.raw_edge = (int*)ws.take(2 * m * 4);
+    w.raw_owner = (int*)ws.take(2 * m * 4);
+    w.adj_nbr = (int*)ws.take(2 * m * 4);
+    w.adj_edge = (int*)ws.take(2 * m * 4);
+    w.flags = (int*)ws.take(TR_FLAG_WORDS * 4);
+    w.pos = (int*)ws.take(d * cap * 4);
+    w.state = (double*)ws.take((long long)cap > tr_lds_limit(lds_node_limit) ? (size_t)tr_groups(num_directions) * 3 * cap * 8 : 0);
+    w.bytes = ws.used;
     return w;
 }
 
@@ -120,28 +92,28 @@ struct TrGraph {  // what the per-index functions read and write
     TrWorkspace w;
 };
 
-TR_HD long long tr_rows(const TrGraph& g) { return g.num_pairs + g.num_meas; }
-TR_HD long long tr_nodes(const TrGraph& g) { return (long long)g.num_images + g.num_tracks; }
-TR_HD double* tr_world_row(const TrGraph& g, long long m) { return m < g.num_pairs ? g.world_pair + 3 * m : g.world_meas + 3 * (m - g.num_pairs); }
+GTSFM_HD long long tr_rows(const TrGraph& g) { return g.num_pairs + g.num_meas; }
+GTSFM_HD long long tr_nodes(const TrGraph& g) { return (long long)g.num_images + g.num_tracks; }
+GTSFM_HD double* tr_world_row(const TrGraph& g, long long m) { return m < g.num_pairs ? g.world_pair + 3 * m : g.world_meas + 3 * (m - g.num_pairs); }
 
 // w = (mx dx + my dy) + mz dz
-TR_HD double tr_project(const double* __restrict__ m, const double* __restrict__ d) { return (m[0] * d[0] + m[1] * d[1]) + m[2] * d[2]; }
+GTSFM_HD double tr_project(const double* __restrict__ m, const double* __restrict__ d) { return (m[0] * d[0] + m[1] * d[1]) + m[2] * d[2]; }
 
-TR_HD void tr_unit(double* v) {
+GTSFM_HD void tr_unit(double* v) {
     const double n = sqrt((v[0] * v[0] + v[1] * v[1]) + v[2] * v[2]);
     v[0] = v[0] / n, v[1] = v[1] / n, v[2] = v[2] / n;
 }
 
 // out = unit(R v), every row of the product summed as (r0 x + r1 y) + r2 z
-TR_HD void tr_rotate_unit(const double* __restrict__ r, const double* v, double* out) {
+GTSFM_HD void tr_rotate_unit(const double* __restrict__ r, const double* v, double* out) {
     for (int k = 0; k < 3; ++k) out[k] = (r[3 * k] * v[0] + r[3 * k + 1] * v[1]) + r[3 * k + 2] * v[2];
     tr_unit(out);
 }
 
-TR_HD double tr_score(double in_w, double out_w) { return in_w < TR_ROOT_EPSILON ? HUGE_VAL : (out_w + 1.0) / (in_w + 1.0); }
+GTSFM_HD double tr_score(double in_w, double out_w) { return in_w < TR_ROOT_EPSILON ? HUGE_VAL : (out_w + 1.0) / (in_w + 1.0); }
 
 // the track of measurement s: the last t with track_off[t] <= s, held inside 0 .. T - 1 whatever the array holds
-TR_HD long long tr_track_of(const TrGraph& g, long long s) {
+GTSFM_HD long long tr_track_of(const TrGraph& g, long long s) {
     long long lo = 0, hi = g.num_tracks - 1;
     while (lo < hi) {
         const long long mid = (lo + hi + 1) / 2;
@@ -152,14 +124,14 @@ TR_HD long long tr_track_of(const TrGraph& g, long long s) {
 
 // ---- phase 1 and 2 ----
 
-TR_HD void tr_init(const TrGraph& g, long long i, uint8_t* __restrict__ camera_inlier) {
+GTSFM_HD void tr_init(const TrGraph& g, long long i, uint8_t* __restrict__ camera_inlier) {
     if (i < TR_FLAG_WORDS) g.w.flags[i] = 0;
     if (i <= tr_nodes(g)) g.w.row_off[i] = 0, g.w.cid[i] = 0;
     if (i < tr_nodes(g)) g.w.cursor[i] = 0;
     if (i < g.num_images) camera_inlier[i] = 0;
 }
 
-TR_HD void tr_edge_table(const TrGraph& g, long long m) {
+GTSFM_HD void tr_edge_table(const TrGraph& g, long long m) {
     const double nan = __builtin_nan("");
     double* out = tr_world_row(g, m);
     double w[3] = {nan, nan, nan};
@@ -202,15 +174,15 @@ TR_HD void tr_edge_table(const TrGraph& g, long long m) {
     out[0] = w[0], out[1] = w[1], out[2] = w[2];
     g.w.key1[m] = k1, g.w.key2[m] = k2;
     if (k1 >= 0) {
-        tr_atomic_add64(&g.w.row_off[k1], 1);
-        tr_atomic_add64(&g.w.row_off[k2], 1);
+        hd_atomic_add(&g.w.row_off[k1], 1);
+        hd_atomic_add(&g.w.row_off[k2], 1);
     }
 }
 
-TR_HD void tr_node_flag(const TrGraph& g, long long n) { g.w.cid[n] = g.w.row_off[n] > 0 ? 1 : 0; }
+GTSFM_HD void tr_node_flag(const TrGraph& g, long long n) { g.w.cid[n] = g.w.row_off[n] > 0 ? 1 : 0; }
 
 // after both scans: the compact offsets
-TR_HD void tr_node_compact(const TrGraph& g, long long n, long long node_capacity) {
+GTSFM_HD void tr_node_compact(const TrGraph& g, long long n, long long node_capacity) {
     const long long c = g.w.cid[n];
     if (n == tr_nodes(g)) {
         if (c <= node_capacity) g.w.coff[c] = g.w.row_off[n];
@@ -219,15 +191,15 @@ TR_HD void tr_node_compact(const TrGraph& g, long long n, long long node_capacit
     }
 }
 
-TR_HD void tr_edge_fill(const TrGraph& g, long long m) {
+GTSFM_HD void tr_edge_fill(const TrGraph& g, long long m) {
     const int k1 = g.w.key1[m], k2 = g.w.key2[m];
     if (k1 < 0) return;
-    const long long s1 = g.w.row_off[k1] + tr_atomic_add(&g.w.cursor[k1], 1), s2 = g.w.row_off[k2] + tr_atomic_add(&g.w.cursor[k2], 1);
+    const long long s1 = g.w.row_off[k1] + hd_atomic_add(&g.w.cursor[k1], 1), s2 = g.w.row_off[k2] + hd_atomic_add(&g.w.cursor[k2], 1);
     if (s1 < g.w.row_off[k1 + 1]) g.w.raw_edge[s1] = (int)m, g.w.raw_owner[s1] = k1;  // always true: exactly degree rows ask
     if (s2 < g.w.row_off[k2 + 1]) g.w.raw_edge[s2] = (int)m, g.w.raw_owner[s2] = k2;
 }
 
-TR_HD void tr_slot_rank(const TrGraph& g, long long s) {
+GTSFM_HD void tr_slot_rank(const TrGraph& g, long long s) {
     if (s >= g.w.row_off[tr_nodes(g)]) return;
     const int edge = g.w.raw_edge[s], owner = g.w.raw_owner[s], k1 = g.w.key1[edge], k2 = g.w.key2[edge];
     const long long lo = g.w.row_off[owner], hi = g.w.row_off[owner + 1];
@@ -255,10 +227,10 @@ struct TrKey {
     int id;
 };
 
-TR_HD TrKey tr_key_max(const TrKey a, const TrKey b) { return (b.score > a.score || (b.score == a.score && b.id < a.id)) ? b : a; }
+GTSFM_HD TrKey tr_key_max(const TrKey a, const TrKey b) { return (b.score > a.score || (b.score == a.score && b.id < a.id)) ? b : a; }
 
 // |w| of list entry j of node c, and whether c is the source of that edge (the edge runs key1 -> key2 when w >= 0, +-0 included)
-TR_HD double tr_entry_weight(const TrGraph& g, long long j, const double* __restrict__ d, bool* node_is_source) {
+GTSFM_HD double tr_entry_weight(const TrGraph& g, long long j, const double* __restrict__ d, bool* node_is_source) {
     const int e2 = g.w.adj_edge[j];
     const double w = tr_project(tr_world_row(g, e2 >> 1), d);
     const bool forward = !(w < 0);
@@ -266,7 +238,7 @@ TR_HD double tr_entry_weight(const TrGraph& g, long long j, const double* __rest
     return fabs(w);
 }
 
-TR_HD void tr_mfas_init_lane(const TrGraph& g, const TrState& st, const double* __restrict__ d, int num_nodes, int lane, int lanes) {
+GTSFM_HD void tr_mfas_init_lane(const TrGraph& g, const TrState& st, const double* __restrict__ d, int num_nodes, int lane, int lanes) {
     for (int c = lane; c < num_nodes; c += lanes) {
         double in_w = 0.0, out_w = 0.0;
         for (long long j = g.w.coff[c]; j < g.w.coff[c + 1]; ++j) {
@@ -278,7 +250,7 @@ TR_HD void tr_mfas_init_lane(const TrGraph& g, const TrState& st, const double* 
     }
 }
 
-TR_HD TrKey tr_mfas_lane_best(const TrState& st, int num_nodes, int lane, int lanes) {
+GTSFM_HD TrKey tr_mfas_lane_best(const TrState& st, int num_nodes, int lane, int lanes) {
     TrKey best = {TR_DEAD, 0x7FFFFFFF};
     for (int c = lane; c < num_nodes; c += lanes) {
         const double s = st.score[c];
@@ -287,7 +259,7 @@ TR_HD TrKey tr_mfas_lane_best(const TrState& st, int num_nodes, int lane, int la
     return best;
 }
 
-TR_HD void tr_mfas_update_lane(const TrGraph& g, const TrState& st, const double* __restrict__ d, int choice, int step, int lane, int lanes) {
+GTSFM_HD void tr_mfas_update_lane(const TrGraph& g, const TrState& st, const double* __restrict__ d, int choice, int step, int lane, int lanes) {
     for (long long j = g.w.coff[choice] + lane; j < g.w.coff[choice + 1]; j += lanes) {
         const int nbr = g.w.adj_nbr[j];
         if (st.score[nbr] == TR_DEAD) continue;
@@ -301,7 +273,7 @@ TR_HD void tr_mfas_update_lane(const TrGraph& g, const TrState& st, const double
 
 // ---- phase 4 ----
 
-TR_HD void tr_row_aggregate(const TrGraph& g, long long m, int num_nodes, double threshold, double* __restrict__ pair_weight, double* __restrict__ meas_weight,
+GTSFM_HD void tr_row_aggregate(const TrGraph& g, long long m, int num_nodes, double threshold, double* __restrict__ pair_weight, double* __restrict__ meas_weight,
                             uint8_t* __restrict__ pair_inlier, uint8_t* __restrict__ meas_inlier, uint8_t* __restrict__ camera_inlier) {
     const int k1 = g.w.key1[m], k2 = g.w.key2[m];
     double mean = __builtin_nan("");
@@ -328,11 +300,11 @@ TR_HD void tr_row_aggregate(const TrGraph& g, long long m, int num_nodes, double
 }
 
 // only add an inlier camera-track measurement if the camera has camera-camera inliers
-TR_HD void tr_meas_filter(const TrGraph& g, long long s, const uint8_t* __restrict__ camera_inlier, uint8_t* __restrict__ meas_inlier) {
+GTSFM_HD void tr_meas_filter(const TrGraph& g, long long s, const uint8_t* __restrict__ camera_inlier, uint8_t* __restrict__ meas_inlier) {
     if (meas_inlier[s] && !camera_inlier[g.image[s]]) meas_inlier[s] = 0;  // an inlier is a valid row: its camera is in range
 }
 
-TR_HD void tr_position_out(const TrGraph& g, long long i, int num_nodes, int* __restrict__ position) {
+GTSFM_HD void tr_position_out(const TrGraph& g, long long i, int num_nodes, int* __restrict__ position) {
     const long long nt = tr_nodes(g), n = i % nt, k = i / nt;
     position[i] = g.w.cid[n + 1] > g.w.cid[n] ? g.w.pos[k * num_nodes + g.w.cid[n]] : -1;
 }
@@ -414,71 +386,22 @@ __global__ __launch_bounds__(TR_THREADS) void tr_mfas_kernel(TrGraph g, int num_
     }
 }
 
-template <class T, class Op>
-__device__ __forceinline__ T tr_block_reduce(T x, T* lds /*[TR_SCAN_THREADS]*/, Op op) {
-    const int tid = threadIdx.x;
-    lds[tid] = x;
-    __syncthreads();
-    for (int off = TR_SCAN_THREADS / 2; off > 0; off >>= 1) {
-        if (tid < off) lds[tid] = op(lds[tid], lds[tid + off]);
-        __syncthreads();
-    }
-    const T all = lds[0];
-    __syncthreads();  // lds is reused
-    return all;
-}
-
 // the counts: one workgroup walks the rows (integer sums by a tree, no atomics on one word)
-__global__ __launch_bounds__(TR_SCAN_THREADS) void tr_counts_kernel(TrGraph g, int num_nodes, const uint8_t* __restrict__ pair_inlier, const uint8_t* __restrict__ meas_inlier,
+__global__ __launch_bounds__(SCAN_THREADS) void tr_counts_kernel(TrGraph g, int num_nodes, const uint8_t* __restrict__ pair_inlier, const uint8_t* __restrict__ meas_inlier,
                                                                    const uint8_t* __restrict__ camera_inlier, int* __restrict__ counts) {
-    __shared__ long long lds[TR_SCAN_THREADS];
+    __shared__ long long lds[SCAN_THREADS];
     long long pe = 0, me = 0, pi = 0, mi = 0, ci = 0;
-    for (long long m = threadIdx.x; m < g.num_pairs; m += TR_SCAN_THREADS) pe += g.w.key1[m] >= 0 ? 1 : 0, pi += pair_inlier[m] ? 1 : 0;
-    for (long long s = threadIdx.x; s < g.num_meas; s += TR_SCAN_THREADS) me += g.w.key1[g.num_pairs + s] >= 0 ? 1 : 0, mi += meas_inlier[s] ? 1 : 0;
-    for (long long c = threadIdx.x; c < g.num_images; c += TR_SCAN_THREADS) ci += camera_inlier[c] ? 1 : 0;
+    for (long long m = threadIdx.x; m < g.num_pairs; m += SCAN_THREADS) pe += g.w.key1[m] >= 0 ? 1 : 0, pi += pair_inlier[m] ? 1 : 0;
+    for (long long s = threadIdx.x; s < g.num_meas; s += SCAN_THREADS) me += g.w.key1[g.num_pairs + s] >= 0 ? 1 : 0, mi += meas_inlier[s] ? 1 : 0;
+    for (long long c = threadIdx.x; c < g.num_images; c += SCAN_THREADS) ci += camera_inlier[c] ? 1 : 0;
     const auto add = [](long long a, long long b) { return a + b; };
-    pe = tr_block_reduce(pe, lds, add), me = tr_block_reduce(me, lds, add), pi = tr_block_reduce(pi, lds, add);
-    mi = tr_block_reduce(mi, lds, add), ci = tr_block_reduce(ci, lds, add);
+    pe = block_reduce<SCAN_THREADS>(pe, lds, add), me = block_reduce<SCAN_THREADS>(me, lds, add), pi = block_reduce<SCAN_THREADS>(pi, lds, add);
+    mi = block_reduce<SCAN_THREADS>(mi, lds, add), ci = block_reduce<SCAN_THREADS>(ci, lds, add);
     if (threadIdx.x == 0) {
         counts[0] = (int)pe, counts[1] = (int)me, counts[2] = num_nodes, counts[3] = (int)pi, counts[4] = (int)mi, counts[5] = (int)ci;
         counts[6] = counts[7] = 0;
     }
 }
-
-// val[0 .. n) -> its exclusive prefix sum in place, val[n] = the total; one workgroup walks the array in blocks
-__global__ __launch_bounds__(TR_SCAN_THREADS) void tr_scan_kernel(long long* val, long long n) {
-    __shared__ long long lds[TR_SCAN_THREADS];
-    const int tid = threadIdx.x;
-    long long carry = 0;
-    for (long long base = 0; base < n; base += TR_SCAN_BLOCK) {  // n and base are uniform: the barriers stay matched
-        const long long at = base + (long long)tid * TR_SCAN_ITEMS;
-        long long x[TR_SCAN_ITEMS], sum = 0;
-#pragma unroll
-        for (int k = 0; k < TR_SCAN_ITEMS; ++k) {
-            x[k] = at + k < n ? val[at + k] : 0;
-            sum += x[k];
-        }
-        lds[tid] = sum;
-        __syncthreads();
-        for (int off = 1; off < TR_SCAN_THREADS; off <<= 1) {
-            const long long add = tid >= off ? lds[tid - off] : 0;
-            __syncthreads();
-            lds[tid] += add;
-            __syncthreads();
-        }
-        long long run = carry + lds[tid] - sum;
-        carry += lds[TR_SCAN_THREADS - 1];
-        __syncthreads();  // lds is reused by the next block
-#pragma unroll
-        for (int k = 0; k < TR_SCAN_ITEMS; ++k) {
-            if (at + k < n) val[at + k] = run;
-            run += x[k];
-        }
-    }
-    if (tid == 0) val[n] = carry;
-}
-
-inline dim3 tr_grid(long long n, long long per_block = TR_THREADS) { return dim3((unsigned)(((n > 0 ? n : 1) + per_block - 1) / per_block)); }
 
 bool tr_sizes_ok(long long num_pairs, long long num_meas, long long num_images, long long num_tracks, long long num_directions, long long node_capacity) {
     return num_pairs >= 0 && num_meas >= 0 && num_images >= 0 && num_tracks >= 0 && num_directions >= 0 && node_capacity >= 0 && num_pairs + num_meas < TR_MAX_ROWS &&
@@ -525,24 +448,24 @@ extern "C" int gtsfm_translation_inliers_f64(const int32_t* pair_images_dev, con
                         nodes, num_directions, node_capacity);
         return GTSFM_ERR_WORKSPACE;
     }
-    const dim3 threads(TR_THREADS), row_grid = tr_grid(rows), node_grid = tr_grid(nodes + 1), scan(TR_SCAN_THREADS);
+    const dim3 threads(TR_THREADS), row_grid = launch_grid(rows, TR_THREADS), node_grid = launch_grid(nodes + 1, TR_THREADS), scan(SCAN_THREADS);
     const long long init_n = nodes + 1 > TR_FLAG_WORDS ? nodes + 1 : TR_FLAG_WORDS;
 
-    hipLaunchKernelGGL(tr_init_kernel, tr_grid(init_n), threads, 0, stream, g, init_n, camera_inlier_dev);
+    hipLaunchKernelGGL(tr_init_kernel, launch_grid(init_n, TR_THREADS), threads, 0, stream, g, init_n, camera_inlier_dev);
     GTSFM_CHECK_LAUNCH("tr_init_kernel");
     hipLaunchKernelGGL(tr_edge_table_kernel, row_grid, threads, 0, stream, g);
     GTSFM_CHECK_LAUNCH("tr_edge_table_kernel");
     hipLaunchKernelGGL(tr_node_flag_kernel, node_grid, threads, 0, stream, g);
     GTSFM_CHECK_LAUNCH("tr_node_flag_kernel");
-    hipLaunchKernelGGL(tr_scan_kernel, dim3(1), scan, 0, stream, g.w.row_off, nodes);
-    GTSFM_CHECK_LAUNCH("tr_scan_kernel");
-    hipLaunchKernelGGL(tr_scan_kernel, dim3(1), scan, 0, stream, g.w.cid, nodes);
-    GTSFM_CHECK_LAUNCH("tr_scan_kernel");
+    hipLaunchKernelGGL(scan_one_workgroup_kernel<long long>, dim3(1), scan, 0, stream, g.w.row_off, nodes);
+    GTSFM_CHECK_LAUNCH("scan_one_workgroup_kernel");
+    hipLaunchKernelGGL(scan_one_workgroup_kernel<long long>, dim3(1), scan, 0, stream, g.w.cid, nodes);
+    GTSFM_CHECK_LAUNCH("scan_one_workgroup_kernel");
     hipLaunchKernelGGL(tr_node_compact_kernel, node_grid, threads, 0, stream, g, node_capacity);
     GTSFM_CHECK_LAUNCH("tr_node_compact_kernel");
     hipLaunchKernelGGL(tr_edge_fill_kernel, row_grid, threads, 0, stream, g);
     GTSFM_CHECK_LAUNCH("tr_edge_fill_kernel");
-    hipLaunchKernelGGL(tr_slot_rank_kernel, tr_grid(2 * rows), threads, 0, stream, g);
+    hipLaunchKernelGGL(tr_slot_rank_kernel, launch_grid(2 * rows, TR_THREADS), threads, 0, stream, g);
     GTSFM_CHECK_LAUNCH("tr_slot_rank_kernel");
     int flags[4] = {0, 0, 0, 0};
     long long graph_nodes = -1;
@@ -571,12 +494,12 @@ extern "C" int gtsfm_translation_inliers_f64(const int32_t* pair_images_dev, con
     hipLaunchKernelGGL(tr_row_aggregate_kernel, row_grid, threads, 0, stream, g, num_nodes, threshold, pair_weight_dev, meas_weight_dev, pair_inlier_dev, meas_inlier_dev,
                        camera_inlier_dev);
     GTSFM_CHECK_LAUNCH("tr_row_aggregate_kernel");
-    hipLaunchKernelGGL(tr_meas_filter_kernel, tr_grid(num_meas), threads, 0, stream, g, camera_inlier_dev, meas_inlier_dev);
+    hipLaunchKernelGGL(tr_meas_filter_kernel, launch_grid(num_meas, TR_THREADS), threads, 0, stream, g, camera_inlier_dev, meas_inlier_dev);
     GTSFM_CHECK_LAUNCH("tr_meas_filter_kernel");
     hipLaunchKernelGGL(tr_counts_kernel, dim3(1), scan, 0, stream, g, num_nodes, pair_inlier_dev, meas_inlier_dev, camera_inlier_dev, counts_dev);
     GTSFM_CHECK_LAUNCH("tr_counts_kernel");
     if (position_dev && num_directions * nodes > 0) {
-        hipLaunchKernelGGL(tr_position_out_kernel, tr_grid(num_directions * nodes), threads, 0, stream, g, num_nodes, num_directions * nodes, position_dev);
+        hipLaunchKernelGGL(tr_position_out_kernel, launch_grid(num_directions * nodes, TR_THREADS), threads, 0, stream, g, num_nodes, num_directions * nodes, position_dev);
         GTSFM_CHECK_LAUNCH("tr_position_out_kernel");
     }
     return GTSFM_OK;

@@ -73,19 +73,14 @@ long long tri_hyp_capacity(long long num_tracks, long long total, long long max_
 
 TriWorkspace tri_layout(void* base, long long num_tracks, long long total, long long max_hyp) {
     TriWorkspace w;
-    size_t used = 0;
-    auto take = [&](size_t bytes) {
-        const size_t at = used;
-        used += align_up(bytes, 256);
-        return (void*)((uintptr_t)base + at);
-    };
+    WorkspaceCarver ws{base, 0};
     w.cap = tri_hyp_capacity(num_tracks, total, max_hyp);
     const size_t cap = w.cap < 0 ? 0 : (size_t)w.cap;
-    w.hyp_off = (long long*)take(((size_t)num_tracks + 1) * 8);
-    w.hyp = (TriHyp*)take(cap * sizeof(TriHyp));
-    w.sel = (int*)take(cap * 4);
-    w.flags = (int*)take(16);
-    w.bytes = used;
+    w.hyp_off = (long long*)ws.take(((size_t)num_tracks + 1) * 8);
+    w.hyp = (TriHyp*)ws.take(cap * sizeof(TriHyp));
+    w.sel = (int*)ws.take(cap * 4);
+    w.flags = (int*)ws.take(16);
+    w.bytes = ws.used;
     return w;
 }
 

@@ -539,27 +539,22 @@ struct TvbaWorkspace {
 
 TvbaWorkspace tvba_layout(void* base, long long num_pairs, long long total) {
     TvbaWorkspace w;
-    size_t used = 0;
-    auto take = [&](size_t bytes) {
-        const size_t at = used;
-        used += align_up(bytes, 256);
-        return (void*)((uintptr_t)base + at);
-    };
+    WorkspaceCarver ws{base, 0};
     const size_t m = (size_t)total, p = (size_t)num_pairs;
-    w.track_off = (long long*)take((m + 1) * 8);
-    w.image = (int*)take(2 * m * 4);
-    w.uv = (float*)take(4 * m * 4);
-    w.cams = (double*)take(2 * p * 17 * 8);
-    w.tri_point = (double*)take(3 * m * 8);
-    w.tri_avg = (double*)take(m * 8);
-    w.tri_exit = (int*)take(m * 4);
-    w.tri_mask = (uint8_t*)take(2 * m);
-    w.tri_stats = (int*)take(4 * m * 4);
-    w.trial = (double*)take(3 * m * 8);
-    w.flags = (int*)take(16);
+    w.track_off = (long long*)ws.take((m + 1) * 8);
+    w.image = (int*)ws.take(2 * m * 4);
+    w.uv = (float*)ws.take(4 * m * 4);
+    w.cams = (double*)ws.take(2 * p * 17 * 8);
+    w.tri_point = (double*)ws.take(3 * m * 8);
+    w.tri_avg = (double*)ws.take(m * 8);
+    w.tri_exit = (int*)ws.take(m * 4);
+    w.tri_mask = (uint8_t*)ws.take(2 * m);
+    w.tri_stats = (int*)ws.take(4 * m * 4);
+    w.trial = (double*)ws.take(3 * m * 8);
+    w.flags = (int*)ws.take(16);
     w.tri_ws_bytes = gtsfm_triangulate_workspace_bytes(total, 2 * total, 0);
-    w.tri_ws = take(w.tri_ws_bytes);
-    w.bytes = used;
+    w.tri_ws = ws.take(w.tri_ws_bytes);
+    w.bytes = ws.used;
     return w;
 }
 

@@ -27,27 +27,22 @@
 //            aggregate: any count is handled by the same loop, no lane or wave capacity exists. A NaN in the segment gives NaN (numpy's
 //            min and median) and the edge is dropped.
 //
-// COMPONENTS (gtsfm_largest_component): the hook / compress rounds of tracks_kernels.hip over the images, with the same invariants
-// (parent[x] <= x, labels only decrease, no kernel waits for another workgroup, the host reads a 4-byte flag per round and refuses after
-// 64). Then the size of every component at its root; the winner is the largest, of equally large ones the owner of the smallest enabled row.
+// COMPONENTS (gtsfm_largest_component): the union-find rounds of graph_prims.h over the images (uf_hook, uf_compress and uf_run_rounds;
+// its header comment states the invariants). Then the size of every component at its root; the winner is the largest, of equally
+// large ones the owner of the smallest enabled row.
 // COUNTS are taken by one workgroup that walks the rows, not by atomics on one word.
 //
-// Every per-index step is a VG_HD function that the kernels call with their global index and tools/view_graph_host_main.cpp calls in
+// Every per-index step is a GTSFM_HD function that the kernels call with their global index and tools/view_graph_host_main.cpp calls in
 // another order on a CPU; the atomics become plain updates there.
 
 #include <math.h>
 
 #include "../../include/gtsfm_amd.h"
-#include "common.h"
+#include "graph_prims.h"
 
-#define VG_HD __host__ __device__ __forceinline__
 #define VG_THREADS 256
 #define VG_WAVE 64
-#define VG_SCAN_THREADS 1024
-#define VG_SCAN_ITEMS 4
-#define VG_SCAN_BLOCK (VG_SCAN_THREADS * VG_SCAN_ITEMS)
-#define VG_MAX_ROUNDS 64
-#define VG_FLAG_WORDS (8 + VG_MAX_ROUNDS)  // word 0: a bad pair; word 1: a duplicate edge; word 8 + r: round r hooked something
+#define VG_FLAG_WORDS UF_FLAG_WORDS  // word 0: a bad pair; word 1: a duplicate edge; word 8 + r: round r hooked something
 #define VG_MAX_EDGES (1ll << 28)
 #define VG_MAX_IMAGES (1ll << 28)
 #define VG_MAX_TRIPLETS ((1ll << 31) / 3)
@@ -57,38 +52,12 @@ typedef unsigned long long vg_u64;
 
 namespace {
 
-VG_HD int vg_atomic_add(int* p, int v) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    return atomicAdd(p, v);
-#else
-    const int old = *p;
-    *p = old + v;
-    return old;
-#endif
-}
-VG_HD long long vg_atomic_add64(long long* p, long long v) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    return (long long)atomicAdd((vg_u64*)p, (vg_u64)v);
-#else
-    const long long old = *p;
-    *p = old + v;
-    return old;
-#endif
-}
-VG_HD void vg_atomic_min(int* p, int v) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    atomicMin(p, v);
-#else
-    if (v < *p) *p = v;
-#endif
-}
-
 // ---- the cycle error ----
 
 // The angle in degrees of M = i2Ri0^T . i2Ri1 . i1Ri0 (products in that order, sums left to right), the way scipy's
 // Rotation.from_matrix(M).as_rotvec() norm finds it: the quaternion from the largest of the diagonal and the trace (the first largest),
 // normalised, then 2 atan2(|q_xyz|, |q_w|).
-VG_HD double vg_cycle_error_deg(const double* __restrict__ i1Ri0, const double* __restrict__ i2Ri1, const double* __restrict__ i2Ri0) {
+GTSFM_HD double vg_cycle_error_deg(const double* __restrict__ i1Ri0, const double* __restrict__ i2Ri1, const double* __restrict__ i2Ri0) {
     double a[9], m[9];
     for (int r = 0; r < 3; ++r)
         for (int c = 0; c < 3; ++c) a[3 * r + c] = i2Ri0[r] * i2Ri1[c] + i2Ri0[3 + r] * i2Ri1[3 + c] + i2Ri0[6 + r] * i2Ri1[6 + c];
@@ -128,27 +97,22 @@ struct VgWorkspace {
 
 VgWorkspace vg_layout(void* base, long long num_edges, long long num_images, long long triplet_capacity) {
     VgWorkspace w;
-    size_t used = 0;
+    WorkspaceCarver ws{base, 0};
     const size_t e = (size_t)num_edges, n = (size_t)num_images;
-    auto take = [&](size_t bytes) {
-        const size_t at = used;
-        used += align_up(bytes, 256);
-        return (void*)((uintptr_t)base + at);
-    };
-    w.row_off = (long long*)take((n + 1) * 8);
-    w.seg_off = (long long*)take((2 * e + 1) * 8);
-    w.trip_off = (long long*)take((2 * e + 1) * 8);
-    w.cursor = (int*)take(n * 4);
-    w.raw_nbr = (int*)take(2 * e * 4);
-    w.raw_edge = (int*)take(2 * e * 4);
-    w.adj_nbr = (int*)take(2 * e * 4);
-    w.adj_edge = (int*)take(2 * e * 4);
-    w.slot_of_edge = (int*)take(e * 4);
-    w.flags = (int*)take(VG_FLAG_WORDS * 4);
-    w.input = (uint8_t*)take(e);
-    w.fixed_bytes = used;
-    w.errs = (double*)take(3 * (size_t)triplet_capacity * 8);
-    w.bytes = used;
+    w.row_off = (long long*)ws.take((n + 1) * 8);
+    w.seg_off = (long long*)ws.take((2 * e + 1) * 8);
+    w.trip_off = (long long*)ws.take((2 * e + 1) * 8);
+    w.cursor = (int*)ws.take(n * 4);
+    w.raw_nbr = (int*)ws.take(2 * e * 4);
+    w.raw_edge = (int*)ws.take(2 * e * 4);
+    w.adj_nbr = (int*)ws.take(2 * e * 4);
+    w.adj_edge = (int*)ws.take(2 * e * 4);
+    w.slot_of_edge = (int*)ws.take(e * 4);
+    w.flags = (int*)ws.take(VG_FLAG_WORDS * 4);
+    w.input = (uint8_t*)ws.take(e);
+    w.fixed_bytes = ws.used;
+    w.errs = (double*)ws.take(3 * (size_t)triplet_capacity * 8);
+    w.bytes = ws.used;
     return w;
 }
 
@@ -162,48 +126,48 @@ struct VgGraph {  // what the per-index functions of the filter read and write
 };
 
 // an enabled row whose pair is in order and in range; every kernel tests it again, so a bad row is never followed anywhere
-VG_HD bool vg_edge_usable(const VgGraph& g, long long e, int* i1, int* i2) {
+GTSFM_HD bool vg_edge_usable(const VgGraph& g, long long e, int* i1, int* i2) {
     if (g.pair_enable && !g.pair_enable[e]) return false;
     *i1 = g.pair_images[2 * e];
     *i2 = g.pair_images[2 * e + 1];
     return *i1 >= 0 && *i1 < *i2 && *i2 < g.num_images;
 }
 
-VG_HD void vg_init(const VgGraph& g, long long i) {
+GTSFM_HD void vg_init(const VgGraph& g, long long i) {
     if (i < VG_FLAG_WORDS) g.w.flags[i] = 0;
     if (i <= g.num_images) g.w.row_off[i] = 0;
     if (i < g.num_images) g.w.cursor[i] = 0;
 }
 
-VG_HD void vg_edge_degree(const VgGraph& g, long long e) {
+GTSFM_HD void vg_edge_degree(const VgGraph& g, long long e) {
     int i1, i2;
     g.w.input[e] = 0;
     if (!vg_edge_usable(g, e, &i1, &i2)) {
         if (!g.pair_enable || g.pair_enable[e]) g.w.flags[0] = 1;
         return;
     }
-    vg_atomic_add64(&g.w.row_off[i1], 1);
-    vg_atomic_add64(&g.w.row_off[i2], 1);
+    hd_atomic_add(&g.w.row_off[i1], 1);
+    hd_atomic_add(&g.w.row_off[i2], 1);
     bool finite = true;
     for (int k = 0; k < 9; ++k) finite = finite && isfinite(g.rotation[9 * e + k]);
     g.w.input[e] = finite ? 1 : 0;
 }
 
-VG_HD void vg_edge_fill(const VgGraph& g, long long e) {
+GTSFM_HD void vg_edge_fill(const VgGraph& g, long long e) {
     int i1, i2;
     if (!vg_edge_usable(g, e, &i1, &i2)) return;
-    const long long s1 = g.w.row_off[i1] + vg_atomic_add(&g.w.cursor[i1], 1), s2 = g.w.row_off[i2] + vg_atomic_add(&g.w.cursor[i2], 1);
+    const long long s1 = g.w.row_off[i1] + hd_atomic_add(&g.w.cursor[i1], 1), s2 = g.w.row_off[i2] + hd_atomic_add(&g.w.cursor[i2], 1);
     if (s1 < g.w.row_off[i1 + 1]) g.w.raw_nbr[s1] = i2, g.w.raw_edge[s1] = (int)e;  // always true: exactly degree rows ask
     if (s2 < g.w.row_off[i2 + 1]) g.w.raw_nbr[s2] = i1, g.w.raw_edge[s2] = (int)e;
 }
 
 // the vertex whose list holds an entry (neighbour, row): the row's other endpoint
-VG_HD int vg_owner(const VgGraph& g, int nbr, int edge) {
+GTSFM_HD int vg_owner(const VgGraph& g, int nbr, int edge) {
     const int i1 = g.pair_images[2 * (long long)edge], i2 = g.pair_images[2 * (long long)edge + 1];
     return i1 == nbr ? i2 : i1;
 }
 
-VG_HD void vg_slot_rank(const VgGraph& g, long long s) {
+GTSFM_HD void vg_slot_rank(const VgGraph& g, long long s) {
     if (s >= g.w.row_off[g.num_images]) return;
     const int nbr = g.w.raw_nbr[s], edge = g.w.raw_edge[s], owner = vg_owner(g, nbr, edge);
     const long long lo = g.w.row_off[owner], hi = g.w.row_off[owner + 1];
@@ -221,7 +185,7 @@ VG_HD void vg_slot_rank(const VgGraph& g, long long s) {
 // The triplets of sorted slot s = edge (a, b) with a < b, by a merge of the two sorted lists. fill == false: seg_off[s] / trip_off[s]
 // receive the counts (all, and those with c > b). fill == true (after the scans): the errors go to the edge's segment, and the triplets
 // this edge owns to the triplet list.
-VG_HD void vg_slot_triplets(const VgGraph& g, long long s, bool fill, int* __restrict__ triplets, double* __restrict__ cycle_error) {
+GTSFM_HD void vg_slot_triplets(const VgGraph& g, long long s, bool fill, int* __restrict__ triplets, double* __restrict__ cycle_error) {
     long long all = 0, own = 0;
     if (s < g.w.row_off[g.num_images]) {
         const int b = g.w.adj_nbr[s], e = g.w.adj_edge[s], a = vg_owner(g, b, e);
@@ -261,7 +225,7 @@ VG_HD void vg_slot_triplets(const VgGraph& g, long long s, bool fill, int* __res
 }
 
 // Lane `lane` of `lanes` for edge row e: see the header comment.
-VG_HD void vg_edge_aggregate(const VgGraph& g, long long e, int lane, int lanes, int criterion, double threshold, int* __restrict__ num_triplets,
+GTSFM_HD void vg_edge_aggregate(const VgGraph& g, long long e, int lane, int lanes, int criterion, double threshold, int* __restrict__ num_triplets,
                              double* __restrict__ aggregate, uint8_t* __restrict__ keep) {
     const double nan = __builtin_nan("");
     if (!g.w.input[e]) {
@@ -309,31 +273,26 @@ struct VgComponents {
 
 VgComponents vg_cc_layout(void* base, long long num_images) {
     VgComponents w;
-    size_t used = 0;
+    WorkspaceCarver ws{base, 0};
     const size_t n = (size_t)num_images;
-    auto take = [&](size_t bytes) {
-        const size_t at = used;
-        used += align_up(bytes, 256);
-        return (void*)((uintptr_t)base + at);
-    };
-    w.parent = (int*)take(n * 4);
-    w.label = (int*)take(n * 4);
-    w.mark = (int*)take(n * 4);
-    w.cnt = (int*)take(n * 4);
-    w.flags = (int*)take(VG_FLAG_WORDS * 4);
-    w.best = (vg_u64*)take(8);
-    w.bytes = used;
+    w.parent = (int*)ws.take(n * 4);
+    w.label = (int*)ws.take(n * 4);
+    w.mark = (int*)ws.take(n * 4);
+    w.cnt = (int*)ws.take(n * 4);
+    w.flags = (int*)ws.take(VG_FLAG_WORDS * 4);
+    w.best = (vg_u64*)ws.take(8);
+    w.bytes = ws.used;
     return w;
 }
 
-VG_HD bool vg_cc_edge(const VgComponents& g, long long e, int* i1, int* i2) {
+GTSFM_HD bool vg_cc_edge(const VgComponents& g, long long e, int* i1, int* i2) {
     if (g.pair_enable && !g.pair_enable[e]) return false;
     *i1 = g.pair_images[2 * e];
     *i2 = g.pair_images[2 * e + 1];
     return *i1 >= 0 && *i1 < g.num_images && *i2 >= 0 && *i2 < g.num_images;
 }
 
-VG_HD void vg_cc_init(const VgComponents& g, long long v) {
+GTSFM_HD void vg_cc_init(const VgComponents& g, long long v) {
     if (v < VG_FLAG_WORDS) g.flags[v] = 0;
     if (v == 0) *g.best = 0;
     if (v >= g.num_images) return;
@@ -341,57 +300,45 @@ VG_HD void vg_cc_init(const VgComponents& g, long long v) {
     g.mark[v] = g.cnt[v] = 0;
 }
 
-VG_HD void vg_cc_hook(const VgComponents& g, long long e, int round) {
+GTSFM_HD void vg_cc_hook(const VgComponents& g, long long e, int round) {
     int u, v;
     if (!vg_cc_edge(g, e, &u, &v)) {
         if (!g.pair_enable || g.pair_enable[e]) g.flags[0] = 1;
         return;
     }
-    if (round == 0) g.mark[u] = 1, g.mark[v] = 1;
-    const int ru = g.label[u], rv = g.label[v];
-    if (ru != rv) {
-        vg_atomic_min(&g.parent[ru > rv ? ru : rv], ru < rv ? ru : rv);
-        g.flags[8 + round] = 1;
-    }
+    uf_hook(g.parent, g.label, g.mark, g.flags, u, v, round);
 }
 
-VG_HD void vg_cc_compress(const VgComponents& g, long long v) {
-    int x = g.parent[v];
-    for (int p = g.parent[x]; p != x; p = g.parent[x]) x = p;  // strictly decreasing: parent[x] <= x
-    g.label[v] = x;
-    g.parent[v] = x;
-}
-
-VG_HD void vg_cc_node_count(const VgComponents& g, long long v) {
-    if (g.mark[v]) vg_atomic_add(&g.cnt[g.label[v]], 1);
+GTSFM_HD void vg_cc_node_count(const VgComponents& g, long long v) {
+    if (g.mark[v]) hd_atomic_add(&g.cnt[g.label[v]], 1);
 }
 
 // The winner is the largest component, and of equally large ones the one that owns the first edge listed: an enabled row bids when its
 // component has the largest size, INT_MAX - row, and the largest bid wins. (A per-root minimum row by atomicMin would put every edge of a
 // connected scene on one word: measured 0.5 ms at 43 867 edges.)
-VG_HD vg_u64 vg_cc_edge_bid(const VgComponents& g, long long e, int largest) {
+GTSFM_HD vg_u64 vg_cc_edge_bid(const VgComponents& g, long long e, int largest) {
     int u, v;
     return vg_cc_edge(g, e, &u, &v) && g.cnt[g.label[u]] == largest ? (vg_u64)(0x7FFFFFFF - e) : 0;
 }
 
 // the winner's label, or -1 without an enabled edge
-VG_HD int vg_cc_root_of_key(const VgComponents& g, vg_u64 best) {
+GTSFM_HD int vg_cc_root_of_key(const VgComponents& g, vg_u64 best) {
     if (best == 0) return -1;
     const long long row = 0x7FFFFFFF - (long long)(unsigned)(best & 0xFFFFFFFFull);
     return g.label[g.pair_images[2 * row]];
 }
 
-VG_HD bool vg_cc_edge_kept(const VgComponents& g, long long e, int root) {
+GTSFM_HD bool vg_cc_edge_kept(const VgComponents& g, long long e, int root) {
     int u, v;
     return root >= 0 && vg_cc_edge(g, e, &u, &v) && g.label[u] == root;
 }
 
-VG_HD void vg_cc_write_node(const VgComponents& g, long long v, uint8_t* __restrict__ node_mask) {
+GTSFM_HD void vg_cc_write_node(const VgComponents& g, long long v, uint8_t* __restrict__ node_mask) {
     const int root = vg_cc_root_of_key(g, *g.best);
     node_mask[v] = (root >= 0 && g.mark[v] && g.label[v] == root) ? 1 : 0;
 }
 
-VG_HD void vg_cc_write_edge(const VgComponents& g, long long e, uint8_t* __restrict__ pair_keep) {
+GTSFM_HD void vg_cc_write_edge(const VgComponents& g, long long e, uint8_t* __restrict__ pair_keep) {
     pair_keep[e] = vg_cc_edge_kept(g, e, vg_cc_root_of_key(g, *g.best)) ? 1 : 0;
 }
 
@@ -436,7 +383,7 @@ __global__ __launch_bounds__(VG_THREADS) void vg_cc_hook_kernel(VgComponents g, 
 }
 __global__ __launch_bounds__(VG_THREADS) void vg_cc_compress_kernel(VgComponents g) {
     VG_INDEX;
-    if (i < g.num_images) vg_cc_compress(g, i);
+    if (i < g.num_images) uf_compress(g.parent, g.label, i);
 }
 __global__ __launch_bounds__(VG_THREADS) void vg_cc_node_count_kernel(VgComponents g) {
     VG_INDEX;
@@ -454,34 +401,20 @@ __global__ __launch_bounds__(VG_THREADS) void vg_cc_write_edge_kernel(VgComponen
 // ---- the counts: ONE workgroup walks the rows and combines by a tree. Tens of thousands of atomics on one word would serialise (measured:
 // 11 ns each, 1.6 ms of the aggregate kernel's 1.65 ms at 48 725 edges); a walk of the same rows by 1024 lanes does not.
 
-template <class T, class Op>
-__device__ __forceinline__ T vg_block_reduce(T x, T* lds /*[VG_SCAN_THREADS]*/, Op op) {
-    const int tid = threadIdx.x;
-    lds[tid] = x;
-    __syncthreads();
-    for (int off = VG_SCAN_THREADS / 2; off > 0; off >>= 1) {
-        if (tid < off) lds[tid] = op(lds[tid], lds[tid + off]);
-        __syncthreads();
-    }
-    const T all = lds[0];
-    __syncthreads();  // lds may be reused
-    return all;
-}
-
-__global__ __launch_bounds__(VG_SCAN_THREADS) void vg_filter_counts_kernel(const uint8_t* __restrict__ input, const uint8_t* __restrict__ keep,
+__global__ __launch_bounds__(SCAN_THREADS) void vg_filter_counts_kernel(const uint8_t* __restrict__ input, const uint8_t* __restrict__ keep,
                                                                           const int* __restrict__ num_triplets, long long num_edges, long long total_triplets,
                                                                           int* __restrict__ counts) {
-    __shared__ long long lds[VG_SCAN_THREADS];
+    __shared__ long long lds[SCAN_THREADS];
     long long in = 0, kept = 0, most = 0;
-    for (long long e = threadIdx.x; e < num_edges; e += VG_SCAN_THREADS) {
+    for (long long e = threadIdx.x; e < num_edges; e += SCAN_THREADS) {
         in += input[e] ? 1 : 0;
         kept += keep[e] ? 1 : 0;
         most = num_triplets[e] > most ? num_triplets[e] : most;
     }
     const auto add = [](long long a, long long b) { return a + b; };
-    in = vg_block_reduce(in, lds, add);
-    kept = vg_block_reduce(kept, lds, add);
-    most = vg_block_reduce(most, lds, [](long long a, long long b) { return a > b ? a : b; });
+    in = block_reduce<SCAN_THREADS>(in, lds, add);
+    kept = block_reduce<SCAN_THREADS>(kept, lds, add);
+    most = block_reduce<SCAN_THREADS>(most, lds, [](long long a, long long b) { return a > b ? a : b; });
     if (threadIdx.x == 0) {
         counts[0] = (int)in, counts[1] = (int)kept, counts[2] = (int)total_triplets, counts[3] = (int)most;
         counts[4] = counts[5] = counts[6] = counts[7] = 0;
@@ -490,69 +423,33 @@ __global__ __launch_bounds__(VG_SCAN_THREADS) void vg_filter_counts_kernel(const
 
 // the largest size and the roots over the nodes, the winning bid over the rows (stored with the size in *g.best for the two write
 // kernels), then the component's edges
-__global__ __launch_bounds__(VG_SCAN_THREADS) void vg_cc_summary_kernel(VgComponents g, int* __restrict__ counts) {
-    __shared__ vg_u64 lds[VG_SCAN_THREADS];
+__global__ __launch_bounds__(SCAN_THREADS) void vg_cc_summary_kernel(VgComponents g, int* __restrict__ counts) {
+    __shared__ vg_u64 lds[SCAN_THREADS];
     vg_u64 largest = 0, components = 0, bid = 0, edges = 0;
-    for (long long v = threadIdx.x; v < g.num_images; v += VG_SCAN_THREADS) {
+    for (long long v = threadIdx.x; v < g.num_images; v += SCAN_THREADS) {
         const vg_u64 size = g.cnt[v] > 0 ? (vg_u64)g.cnt[v] : 0;  // cnt is nonzero at the roots of components with an edge only
         components += size ? 1 : 0;
         largest = size > largest ? size : largest;
     }
     const auto add = [](vg_u64 a, vg_u64 b) { return a + b; };
     const auto most = [](vg_u64 a, vg_u64 b) { return a > b ? a : b; };
-    largest = vg_block_reduce(largest, lds, most);
-    components = vg_block_reduce(components, lds, add);
-    for (long long e = threadIdx.x; e < g.num_edges && largest; e += VG_SCAN_THREADS) {
+    largest = block_reduce<SCAN_THREADS>(largest, lds, most);
+    components = block_reduce<SCAN_THREADS>(components, lds, add);
+    for (long long e = threadIdx.x; e < g.num_edges && largest; e += SCAN_THREADS) {
         const vg_u64 b = vg_cc_edge_bid(g, e, (int)largest);
         bid = b > bid ? b : bid;
     }
-    bid = vg_block_reduce(bid, lds, most);
+    bid = block_reduce<SCAN_THREADS>(bid, lds, most);
     const vg_u64 best = largest ? (largest << 32) | bid : 0;
     const int root = vg_cc_root_of_key(g, best);
-    for (long long e = threadIdx.x; e < g.num_edges; e += VG_SCAN_THREADS) edges += vg_cc_edge_kept(g, e, root) ? 1 : 0;
-    edges = vg_block_reduce(edges, lds, add);
+    for (long long e = threadIdx.x; e < g.num_edges; e += SCAN_THREADS) edges += vg_cc_edge_kept(g, e, root) ? 1 : 0;
+    edges = block_reduce<SCAN_THREADS>(edges, lds, add);
     if (threadIdx.x == 0) {
         *g.best = best;
         counts[0] = (int)(best >> 32), counts[1] = (int)edges, counts[2] = (int)components;
         counts[3] = counts[4] = counts[5] = counts[6] = counts[7] = 0;
     }
 }
-
-// val[0 .. n) -> its exclusive prefix sum in place, val[n] = the total. One workgroup walks the array in blocks of VG_SCAN_BLOCK: the
-// arrays here are a few hundred thousand entries at most, and a single launch keeps the carry in a register.
-__global__ __launch_bounds__(VG_SCAN_THREADS) void vg_scan_kernel(long long* val, long long n) {
-    __shared__ long long lds[VG_SCAN_THREADS];
-    const int tid = threadIdx.x;
-    long long carry = 0;
-    for (long long base = 0; base < n; base += VG_SCAN_BLOCK) {  // n and base are uniform: the barriers stay matched
-        const long long at = base + (long long)tid * VG_SCAN_ITEMS;
-        long long x[VG_SCAN_ITEMS], sum = 0;
-#pragma unroll
-        for (int k = 0; k < VG_SCAN_ITEMS; ++k) {
-            x[k] = at + k < n ? val[at + k] : 0;
-            sum += x[k];
-        }
-        lds[tid] = sum;
-        __syncthreads();
-        for (int off = 1; off < VG_SCAN_THREADS; off <<= 1) {
-            const long long add = tid >= off ? lds[tid - off] : 0;
-            __syncthreads();
-            lds[tid] += add;
-            __syncthreads();
-        }
-        long long run = carry + lds[tid] - sum;
-        carry += lds[VG_SCAN_THREADS - 1];
-        __syncthreads();  // lds is reused by the next block
-#pragma unroll
-        for (int k = 0; k < VG_SCAN_ITEMS; ++k) {
-            if (at + k < n) val[at + k] = run;
-            run += x[k];
-        }
-    }
-    if (tid == 0) val[n] = carry;
-}
-
-inline dim3 vg_grid(long long n, long long per_block = VG_THREADS) { return dim3((unsigned)((n > 0 ? n : 1) + per_block - 1) / (unsigned)per_block); }
 
 }  // namespace
 
@@ -591,15 +488,15 @@ extern "C" int gtsfm_view_graph_cycle_filter_f64(const int32_t* pair_images_dev,
                         triplet_capacity);
         return GTSFM_ERR_WORKSPACE;
     }
-    const dim3 threads(VG_THREADS), edge_grid = vg_grid(num_edges), slot_grid = vg_grid(2 * num_edges);
+    const dim3 threads(VG_THREADS), edge_grid = launch_grid(num_edges, VG_THREADS), slot_grid = launch_grid(2 * num_edges, VG_THREADS);
     const long long init_n = (long long)num_images + 1 > VG_FLAG_WORDS ? (long long)num_images + 1 : VG_FLAG_WORDS;
 
-    hipLaunchKernelGGL(vg_init_kernel, vg_grid(init_n), threads, 0, stream, g, init_n);
+    hipLaunchKernelGGL(vg_init_kernel, launch_grid(init_n, VG_THREADS), threads, 0, stream, g, init_n);
     GTSFM_CHECK_LAUNCH("vg_init_kernel");
     hipLaunchKernelGGL(vg_edge_degree_kernel, edge_grid, threads, 0, stream, g);
     GTSFM_CHECK_LAUNCH("vg_edge_degree_kernel");
-    hipLaunchKernelGGL(vg_scan_kernel, dim3(1), dim3(VG_SCAN_THREADS), 0, stream, g.w.row_off, (long long)num_images);
-    GTSFM_CHECK_LAUNCH("vg_scan_kernel");
+    hipLaunchKernelGGL(scan_one_workgroup_kernel<long long>, dim3(1), dim3(SCAN_THREADS), 0, stream, g.w.row_off, (long long)num_images);
+    GTSFM_CHECK_LAUNCH("scan_one_workgroup_kernel");
     hipLaunchKernelGGL(vg_edge_fill_kernel, edge_grid, threads, 0, stream, g);
     GTSFM_CHECK_LAUNCH("vg_edge_fill_kernel");
     hipLaunchKernelGGL(vg_slot_rank_kernel, slot_grid, threads, 0, stream, g);
@@ -614,10 +511,10 @@ extern "C" int gtsfm_view_graph_cycle_filter_f64(const int32_t* pair_images_dev,
 
     hipLaunchKernelGGL(vg_slot_triplets_kernel, slot_grid, threads, 0, stream, g, 0, (int*)nullptr, (double*)nullptr);
     GTSFM_CHECK_LAUNCH("vg_slot_triplets_kernel");
-    hipLaunchKernelGGL(vg_scan_kernel, dim3(1), dim3(VG_SCAN_THREADS), 0, stream, g.w.seg_off, 2 * num_edges);
-    GTSFM_CHECK_LAUNCH("vg_scan_kernel");
-    hipLaunchKernelGGL(vg_scan_kernel, dim3(1), dim3(VG_SCAN_THREADS), 0, stream, g.w.trip_off, 2 * num_edges);
-    GTSFM_CHECK_LAUNCH("vg_scan_kernel");
+    hipLaunchKernelGGL(scan_one_workgroup_kernel<long long>, dim3(1), dim3(SCAN_THREADS), 0, stream, g.w.seg_off, 2 * num_edges);
+    GTSFM_CHECK_LAUNCH("scan_one_workgroup_kernel");
+    hipLaunchKernelGGL(scan_one_workgroup_kernel<long long>, dim3(1), dim3(SCAN_THREADS), 0, stream, g.w.trip_off, 2 * num_edges);
+    GTSFM_CHECK_LAUNCH("scan_one_workgroup_kernel");
     long long totals[2] = {-1, -1};  // entries of the per-edge lists, distinct triplets
     if (hipMemcpyAsync(&totals[0], g.w.seg_off + 2 * num_edges, 8, hipMemcpyDeviceToHost, stream) != hipSuccess ||
         hipMemcpyAsync(&totals[1], g.w.trip_off + 2 * num_edges, 8, hipMemcpyDeviceToHost, stream) != hipSuccess || hipStreamSynchronize(stream) != hipSuccess) {
@@ -633,10 +530,10 @@ extern "C" int gtsfm_view_graph_cycle_filter_f64(const int32_t* pair_images_dev,
 
     hipLaunchKernelGGL(vg_slot_triplets_kernel, slot_grid, threads, 0, stream, g, 1, triplets_dev, cycle_error_dev);
     GTSFM_CHECK_LAUNCH("vg_slot_triplets_kernel");
-    hipLaunchKernelGGL(vg_edge_aggregate_kernel, vg_grid(num_edges, VG_THREADS / VG_WAVE), threads, 0, stream, g, criterion, error_threshold, num_triplets_dev,
+    hipLaunchKernelGGL(vg_edge_aggregate_kernel, launch_grid(num_edges, VG_THREADS / VG_WAVE), threads, 0, stream, g, criterion, error_threshold, num_triplets_dev,
                        aggregate_error_dev, keep_dev);
     GTSFM_CHECK_LAUNCH("vg_edge_aggregate_kernel");
-    hipLaunchKernelGGL(vg_filter_counts_kernel, dim3(1), dim3(VG_SCAN_THREADS), 0, stream, g.w.input, keep_dev, num_triplets_dev, num_edges, totals[1], counts_dev);
+    hipLaunchKernelGGL(vg_filter_counts_kernel, dim3(1), dim3(SCAN_THREADS), 0, stream, g.w.input, keep_dev, num_triplets_dev, num_edges, totals[1], counts_dev);
     GTSFM_CHECK_LAUNCH("vg_filter_counts_kernel");
     return GTSFM_OK;
 }
@@ -655,34 +552,36 @@ extern "C" int gtsfm_largest_component(const int32_t* pair_images_dev, const uin
         gtsfm_set_error("%s: workspace of %zu bytes, %zu needed for %d images", me, workspace_bytes, g.bytes, num_images);
         return GTSFM_ERR_WORKSPACE;
     }
-    const dim3 threads(VG_THREADS), edge_grid = vg_grid(num_edges), node_grid = vg_grid(num_images);
+    const dim3 threads(VG_THREADS), edge_grid = launch_grid(num_edges, VG_THREADS), node_grid = launch_grid(num_images, VG_THREADS);
     const long long init_n = num_images > VG_FLAG_WORDS ? num_images : VG_FLAG_WORDS;
-    hipLaunchKernelGGL(vg_cc_init_kernel, vg_grid(init_n), threads, 0, stream, g, init_n);
+    hipLaunchKernelGGL(vg_cc_init_kernel, launch_grid(init_n, VG_THREADS), threads, 0, stream, g, init_n);
     GTSFM_CHECK_LAUNCH("vg_cc_init_kernel");
-    for (int rounds = 0; num_edges > 0;) {
-        if (rounds == VG_MAX_ROUNDS) {
-            gtsfm_set_error("%s: no fixed point after %d rounds (%d images, %lld edges); nothing was written", me, rounds, num_images, num_edges);
-            return GTSFM_ERR_INVALID;
-        }
-        hipLaunchKernelGGL(vg_cc_hook_kernel, edge_grid, threads, 0, stream, g, rounds);
-        GTSFM_CHECK_LAUNCH("vg_cc_hook_kernel");
-        hipLaunchKernelGGL(vg_cc_compress_kernel, node_grid, threads, 0, stream, g);
-        GTSFM_CHECK_LAUNCH("vg_cc_compress_kernel");
-        int flag[2] = {0, 0};  // bad input, this round hooked
-        if (hipMemcpyAsync(&flag[0], g.flags, sizeof(int), hipMemcpyDeviceToHost, stream) != hipSuccess ||
-            hipMemcpyAsync(&flag[1], g.flags + 8 + rounds, sizeof(int), hipMemcpyDeviceToHost, stream) != hipSuccess || hipStreamSynchronize(stream) != hipSuccess) {
+    if (num_edges > 0) {
+        const auto hook = [&](int round) -> int {
+            hipLaunchKernelGGL(vg_cc_hook_kernel, edge_grid, threads, 0, stream, g, round);
+            GTSFM_CHECK_LAUNCH("vg_cc_hook_kernel");
+            return GTSFM_OK;
+        };
+        const auto compress = [&]() -> int {
+            hipLaunchKernelGGL(vg_cc_compress_kernel, node_grid, threads, 0, stream, g);
+            GTSFM_CHECK_LAUNCH("vg_cc_compress_kernel");
+            return GTSFM_OK;
+        };
+        int rounds = 0;
+        const UfOutcome labelled = uf_run_rounds(g.flags, stream, hook, compress, &rounds);
+        if (labelled == UF_LAUNCH_FAILED) return GTSFM_ERR_HIP;
+        if (labelled == UF_READ_FAILED) {
             gtsfm_set_error("%s: round %d failed: %s", me, rounds, hipGetErrorString(hipGetLastError()));
             return GTSFM_ERR_HIP;
         }
-        GTSFM_CHECK_ARG(!flag[0], "%s: an enabled edge names an image outside 0 .. %d; nothing was written", me, num_images - 1);
-        ++rounds;
-        if (!flag[1]) break;
+        GTSFM_CHECK_ARG(labelled != UF_NO_FIXED_POINT, "%s: no fixed point after %d rounds (%d images, %lld edges); nothing was written", me, rounds, num_images, num_edges);
+        GTSFM_CHECK_ARG(labelled != UF_BAD_INPUT, "%s: an enabled edge names an image outside 0 .. %d; nothing was written", me, num_images - 1);
     }
     if (num_edges > 0) {
         hipLaunchKernelGGL(vg_cc_node_count_kernel, node_grid, threads, 0, stream, g);
         GTSFM_CHECK_LAUNCH("vg_cc_node_count_kernel");
     }
-    hipLaunchKernelGGL(vg_cc_summary_kernel, dim3(1), dim3(VG_SCAN_THREADS), 0, stream, g, counts_dev);
+    hipLaunchKernelGGL(vg_cc_summary_kernel, dim3(1), dim3(SCAN_THREADS), 0, stream, g, counts_dev);
     GTSFM_CHECK_LAUNCH("vg_cc_summary_kernel");
     hipLaunchKernelGGL(vg_cc_write_node_kernel, node_grid, threads, 0, stream, g, node_mask_dev);
     GTSFM_CHECK_LAUNCH("vg_cc_write_node_kernel");

@@ -5,36 +5,27 @@ zeroed memory and with the device's 256-lane partition, last lane first, over me
 well; all must be byte-equal to each other and to the restatement (tests/rotation_averaging_reference.py): rotations, mask, counters and
 costs. The program runs as its own process; no sanitizer is loaded into Python and no GPU is involved."""
 
-import os
 import shutil
 import struct
-import subprocess
 
 import numpy as np
 import pytest
 
-from gtsfm_amd.csrc.build import ARCH, HIPCC
+from gtsfm_amd.csrc.build import HIPCC
 from tests import rotation_averaging_reference as ref
 from tests import rotation_averaging_scenes as scenes
 from tests.conftest import REPO
+from tests.hostbuild_program import build_program, run
 
 pytestmark = pytest.mark.skipif(shutil.which(HIPCC) is None, reason="hipcc is not installed")
 
 SOURCE = REPO / "tools" / "rotation_averaging_host_main.cpp"
-FLAGS = [f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-ffp-contract=off", "-Wall", "-Wno-unused-function"]  # gtsfm_amd/csrc/build.py's
-SANITIZE = "-fsanitize=address,undefined"
 MAGIC = 0x3147564154524D46
 
 
 @pytest.fixture(scope="module", params=["plain", "sanitized"])
 def program(request, tmp_path_factory):
-    d = tmp_path_factory.mktemp(f"rotation_averaging_host_{request.param}")
-    san = request.param == "sanitized"
-    obj, exe = d / "main.o", d / "rotation_averaging_host"
-    # the device side ignores the host-only flag; the link step takes it plain
-    subprocess.run([HIPCC, *FLAGS, *(["-Xarch_host", SANITIZE] if san else []), "-c", str(SOURCE), "-o", str(obj)], check=True, capture_output=True, timeout=600)
-    subprocess.run([HIPCC, *([SANITIZE] if san else []), str(obj), "-o", str(exe)], check=True, capture_output=True, timeout=600)
-    return exe, d
+    return build_program(tmp_path_factory, SOURCE, request.param == "sanitized")
 
 
 def write_scene(path, pair_images, rotation, weight, pair_enable, num_images, row_off, anchor, opts):
@@ -51,10 +42,7 @@ def run_program(program, pair_images, rotation, weight, pair_enable, num_images,
     path, out_path = d / "scene.bin", d / "out.bin"
     write_scene(path, pair_images, rotation, weight, pair_enable, num_images, row_off, anchor, opts)
     out_path.unlink(missing_ok=True)
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0", UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1")
-    done = subprocess.run([str(exe), str(path), str(out_path)], capture_output=True, text=True, timeout=600, env=env)
-    assert done.returncode == expect_status, f"exit status {done.returncode}\n{done.stderr[-3000:]}"
-    assert "runtime error" not in done.stderr and "Sanitizer" not in done.stderr, done.stderr[-3000:]
+    done = run(exe, [path, out_path], expect_status)
     if expect_status:
         return done.stderr
     raw, p, n = out_path.read_bytes(), len(row_off) - 1, num_images

@@ -1,39 +1,30 @@
-"""CPU: the 1DSfM kernels' own per-lane functions (the TR_HD functions of gtsfm_amd/csrc/translation_kernels.hip), compiled for the host into
+"""CPU: the 1DSfM kernels' own per-lane functions (the GTSFM_HD functions of gtsfm_amd/csrc/translation_kernels.hip), compiled for the host into
 the stand-alone program tools/translation_inliers_host_main.cpp -- once plain and once with the host's address and undefined-behaviour
 sanitizers -- on every scene of tests/translation_inliers_scenes.py. The program runs each scene twice -- one lane, ascending indices, zeroed
 memory; the device's 256-lane partition, descending indices, memory filled with 0xFF -- and the two outputs must be byte-equal to each other
 and to the restatement (tests/translation_inliers_reference.py), positions included. The program runs as its own process; no sanitizer is
 loaded into Python and no GPU is involved."""
 
-import os
 import shutil
 import struct
-import subprocess
 
 import numpy as np
 import pytest
 
-from gtsfm_amd.csrc.build import ARCH, HIPCC
+from gtsfm_amd.csrc.build import HIPCC
 from tests import translation_inliers_scenes as scenes
 from tests.conftest import REPO
+from tests.hostbuild_program import build_program, run
 
 pytestmark = pytest.mark.skipif(shutil.which(HIPCC) is None, reason="hipcc is not installed")
 
 SOURCE = REPO / "tools" / "translation_inliers_host_main.cpp"
-FLAGS = [f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-ffp-contract=off", "-Wall", "-Wno-unused-function"]  # gtsfm_amd/csrc/build.py's
-SANITIZE = "-fsanitize=address,undefined"
 MAGIC = 0x31534E4952544D46
 
 
 @pytest.fixture(scope="module", params=["plain", "sanitized"])
 def program(request, tmp_path_factory):
-    d = tmp_path_factory.mktemp(f"translation_inliers_host_{request.param}")
-    san = request.param == "sanitized"
-    obj, exe = d / "main.o", d / "translation_inliers_host"
-    # the device side ignores the host-only flag; the link step takes it plain
-    subprocess.run([HIPCC, *FLAGS, *(["-Xarch_host", SANITIZE] if san else []), "-c", str(SOURCE), "-o", str(obj)], check=True, capture_output=True, timeout=600)
-    subprocess.run([HIPCC, *([SANITIZE] if san else []), str(obj), "-o", str(exe)], check=True, capture_output=True, timeout=600)
-    return exe, d
+    return build_program(tmp_path_factory, SOURCE, request.param == "sanitized")
 
 
 def write_scene(path, sc):
@@ -56,10 +47,7 @@ def run_program(program, sc, expect_status=0):
     path, out_path = d / "scene.bin", d / "out.bin"
     e, s, n, t, dn = write_scene(path, sc)
     out_path.unlink(missing_ok=True)
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0", UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1")
-    done = subprocess.run([str(exe), str(path), str(out_path)], capture_output=True, text=True, timeout=600, env=env)
-    assert done.returncode == expect_status, f"exit status {done.returncode}\n{done.stderr[-3000:]}"
-    assert "runtime error" not in done.stderr and "Sanitizer" not in done.stderr, done.stderr[-3000:]
+    done = run(exe, [path, out_path], expect_status)
     if expect_status:
         return done.stderr
     raw = out_path.read_bytes()

@@ -4,37 +4,28 @@ undefined-behaviour sanitizers -- and held to the rule the device is held to (``
 restatement's existing rule on ``small_shapes()``). The program itself requires its two lane partitions (one lane; the device's
 select / grid-stride pattern over a workspace filled with 0xFF) to give byte-equal outputs. No GPU is involved."""
 
-import os
 import shutil
 import struct
-import subprocess
 
 import numpy as np
 import pytest
 
-from gtsfm_amd.csrc.build import ARCH, HIPCC
+from gtsfm_amd.csrc.build import HIPCC
 from tests import triangulation_reference as ref
 from tests import triangulation_scenes as scenes
 from tests.conftest import REPO
+from tests.hostbuild_program import build_program, run
 from tests.test_triangulation_arbiter_host import FAMILIES, held_to_rule
 
 pytestmark = pytest.mark.skipif(shutil.which(HIPCC) is None, reason="hipcc is not installed")
 
 SOURCE = REPO / "tools" / "triangulation_host_main.cpp"
-FLAGS = [f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-ffp-contract=off", "-Wall", "-Wno-unused-function"]  # gtsfm_amd/csrc/build.py's
-SANITIZE = "-fsanitize=address,undefined"
 MAGIC = 0x3149525453464754
 
 
 @pytest.fixture(scope="module", params=["plain", "sanitized"])
 def program(request, tmp_path_factory):
-    d = tmp_path_factory.mktemp(f"triangulation_host_{request.param}")
-    san = request.param == "sanitized"
-    obj, exe = d / "main.o", d / "triangulation_host"
-    # the device side ignores the host-only flag; the link step takes it plain
-    subprocess.run([HIPCC, *FLAGS, *(["-Xarch_host", SANITIZE] if san else []), "-c", str(SOURCE), "-o", str(obj)], check=True, capture_output=True, timeout=600)
-    subprocess.run([HIPCC, *([SANITIZE] if san else []), str(obj), "-o", str(exe)], check=True, capture_output=True, timeout=600)
-    return exe, d
+    return build_program(tmp_path_factory, SOURCE, request.param == "sanitized")
 
 
 def run_program(program, scene, expect_status=0, **opts):
@@ -48,10 +39,7 @@ def run_program(program, scene, expect_status=0, **opts):
         for a, dt in ((off, np.int64), (image, np.int32), (uv, np.float32), (table, np.float64)):
             f.write(np.ascontiguousarray(a, dtype=dt).tobytes())
     out_path.unlink(missing_ok=True)
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0", UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1")
-    done = subprocess.run([str(exe), str(path), str(out_path)], capture_output=True, text=True, timeout=600, env=env)
-    assert done.returncode == expect_status, f"exit status {done.returncode}\n{done.stderr[-3000:]}"
-    assert "runtime error" not in done.stderr and "Sanitizer" not in done.stderr, done.stderr[-3000:]
+    done = run(exe, [path, out_path], expect_status)
     if expect_status:
         return done.stderr
     raw = out_path.read_bytes()

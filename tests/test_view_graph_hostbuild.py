@@ -1,40 +1,31 @@
-"""CPU: the view-graph kernels' own per-index functions (the VG_HD functions of gtsfm_amd/csrc/view_graph_kernels.hip), compiled for the host
+"""CPU: the view-graph kernels' own per-index functions (the GTSFM_HD functions of gtsfm_amd/csrc/view_graph_kernels.hip), compiled for the host
 into the stand-alone program tools/view_graph_host_main.cpp -- once plain and once with the host's address and undefined-behaviour
 sanitizers -- on every scene of tests/view_graph_scenes.py, held to the rule the device is held to (tests/test_view_graph_gpu.py): the
 discrete outputs equal the restatement's, the values lie within the measured tolerance. The program itself requires its two runs to give
 byte-equal outputs: ascending indices with one lane per edge over zeroed memory against descending indices with 64 lanes per edge over
 memory filled with 0xFF. No GPU is involved. The distances go to profiles/view_graph_host_tests.txt by hand (``-s`` shows them)."""
 
-import os
 import shutil
 import struct
-import subprocess
 
 import numpy as np
 import pytest
 
-from gtsfm_amd.csrc.build import ARCH, HIPCC
+from gtsfm_amd.csrc.build import HIPCC
 from tests import view_graph_reference as ref
 from tests import view_graph_scenes as scenes
 from tests.conftest import REPO
+from tests.hostbuild_program import build_program, run
 
 pytestmark = pytest.mark.skipif(shutil.which(HIPCC) is None, reason="hipcc is not installed")
 
 SOURCE = REPO / "tools" / "view_graph_host_main.cpp"
-FLAGS = [f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-ffp-contract=off", "-Wall", "-Wno-unused-function"]  # gtsfm_amd/csrc/build.py's
-SANITIZE = "-fsanitize=address,undefined"
 MAGIC = 0x3148505247574956
 
 
 @pytest.fixture(scope="module", params=["plain", "sanitized"])
 def program(request, tmp_path_factory):
-    d = tmp_path_factory.mktemp(f"view_graph_host_{request.param}")
-    san = request.param == "sanitized"
-    obj, exe = d / "main.o", d / "view_graph_host"
-    # the device side ignores the host-only flag; the link step takes it plain
-    subprocess.run([HIPCC, *FLAGS, *(["-Xarch_host", SANITIZE] if san else []), "-c", str(SOURCE), "-o", str(obj)], check=True, capture_output=True, timeout=600)
-    subprocess.run([HIPCC, *([SANITIZE] if san else []), str(obj), "-o", str(exe)], check=True, capture_output=True, timeout=600)
-    return exe, d
+    return build_program(tmp_path_factory, SOURCE, request.param == "sanitized")
 
 
 def run_program(program, sc, criterion, threshold, expect_status=0):
@@ -48,10 +39,7 @@ def run_program(program, sc, criterion, threshold, expect_status=0):
         f.write(struct.pack("<8d", threshold, 0, 0, 0, 0, 0, 0, 0))
         f.write(pairs.tobytes() + rot.tobytes() + enable.tobytes())
     out_path.unlink(missing_ok=True)
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0", UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1")
-    done = subprocess.run([str(exe), str(path), str(out_path)], capture_output=True, text=True, timeout=600, env=env)
-    assert done.returncode == expect_status, f"exit status {done.returncode}\n{done.stderr[-3000:]}"
-    assert "runtime error" not in done.stderr and "Sanitizer" not in done.stderr, done.stderr[-3000:]
+    done = run(exe, [path, out_path], expect_status)
     if expect_status:
         return done.stderr
     raw = out_path.read_bytes()

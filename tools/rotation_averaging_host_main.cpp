@@ -16,21 +16,8 @@
 // status 3: the input is refused, with the reason on stderr; 1: a bad file. Every input array is a heap allocation of its exact size, so a
 // read outside it is a sanitizer report.
 
-#include <stdarg.h>
-#include <stdlib.h>
-#include <string.h>
-
-#include <vector>
-
 #include "../gtsfm_amd/csrc/rotation_averaging_kernels.hip"
-
-void gtsfm_set_error(const char* fmt, ...) {
-    va_list args;
-    va_start(args, fmt);
-    vfprintf(stderr, fmt, args);
-    va_end(args);
-    fputc('\n', stderr);
-}
+#include "host_main_common.h"
 
 namespace {
 
@@ -44,13 +31,6 @@ struct Scene {
     uint8_t* pair_enable;
     long long* row_off;
 };
-
-template <class T>
-T* read_array(FILE* f, size_t n, bool* ok) {
-    T* p = (T*)malloc(n ? n * sizeof(T) : 1);  // exact size: the sanitizer sees every read past the end
-    if (!p || (n && fread(p, sizeof(T), n, f) != n)) *ok = false;
-    return p;
-}
 
 bool read_scene(const char* path, Scene& s) {
     FILE* f = fopen(path, "rb");
@@ -77,13 +57,6 @@ struct Outputs {
     std::vector<int> counters;
 };
 
-template <class T>
-void fill_vector(std::vector<T>& v, size_t n, int fill) {
-    v.assign(n + 1, T());  // one spare element: data() is never null
-    memset(v.data(), fill, (n + 1) * sizeof(T));
-    v.resize(n);
-}
-
 // 0: done; 3: refused
 int run(const Scene& s, int lanes, bool descending, int fill, Outputs& out) {
     const size_t P = s.P, N = s.N;
@@ -93,8 +66,7 @@ int run(const Scene& s, int lanes, bool descending, int fill, Outputs& out) {
         return 3;
     }
     const size_t bytes = ra_layout(nullptr, s.E, s.N, s.P).bytes;
-    void* ws = aligned_alloc(256, align_up(bytes ? bytes : 1, 256));
-    memset(ws, fill, align_up(bytes ? bytes : 1, 256));
+    void* ws = filled(bytes, fill);
     RaArgs a{s.pair_images, s.rotation, s.weight, s.has_enable ? s.pair_enable : nullptr, s.row_off, s.E, (int)s.N, (int)s.P, (int)s.anchor, s.chordal_tol, s.delta0,
              s.kappa_cg, s.theta, s.gradient_tol, (int)s.chordal_cap, (int)s.max_outer, (int)s.max_inner, ra_layout(ws, s.E, s.N, s.P), out.wri.data(),
              out.node_valid.data(), out.counters.data(), out.costs.data()};
@@ -113,18 +85,8 @@ int run(const Scene& s, int lanes, bool descending, int fill, Outputs& out) {
 }
 
 template <class T>
-bool same(const std::vector<T>& a, const std::vector<T>& b) {
-    return a.size() == b.size() && (a.empty() || memcmp(a.data(), b.data(), a.size() * sizeof(T)) == 0);
-}
-
-template <class T>
 bool same_slice(const std::vector<T>& all, size_t at, const std::vector<T>& one) {
     return one.empty() || memcmp(all.data() + at, one.data(), one.size() * sizeof(T)) == 0;
-}
-
-template <class T>
-bool write_vector(FILE* f, const std::vector<T>& v) {
-    return v.empty() || fwrite(v.data(), sizeof(T), v.size(), f) == v.size();
 }
 
 }  // namespace

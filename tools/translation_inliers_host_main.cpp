@@ -1,4 +1,4 @@
-// Stand-alone host build of the 1DSfM kernels' per-lane functions (the TR_HD functions of gtsfm_amd/csrc/translation_kernels.hip: the edge
+// Stand-alone host build of the 1DSfM kernels' per-lane functions (the GTSFM_HD functions of gtsfm_amd/csrc/translation_kernels.hip: the edge
 // table, the adjacency, the MFAS ordering, the per-row aggregate), for running them on a CPU and under the host sanitizers:
 //
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off [-Xarch_host -fsanitize=address,undefined] -c tools/translation_inliers_host_main.cpp -o main.o
@@ -18,21 +18,8 @@
 // The two outputs must be byte-equal (exit status 2 when they are not). Exit status 3: the input is refused, with the reason on stderr; 1:
 // a bad file. Every input array is a heap allocation of its exact size, so a read outside it is a sanitizer report.
 
-#include <stdarg.h>
-#include <stdlib.h>
-#include <string.h>
-
-#include <vector>
-
 #include "../gtsfm_amd/csrc/translation_kernels.hip"
-
-void gtsfm_set_error(const char* fmt, ...) {
-    va_list args;
-    va_start(args, fmt);
-    vfprintf(stderr, fmt, args);
-    va_end(args);
-    fputc('\n', stderr);
-}
+#include "host_main_common.h"
 
 namespace {
 
@@ -47,13 +34,6 @@ struct Scene {
     long long* track_off;
     float* uv;
 };
-
-template <class T>
-T* read_array(FILE* f, size_t n, bool* ok) {
-    T* p = (T*)malloc(n ? n * sizeof(T) : 1);  // exact size: the sanitizer sees every read past the end
-    if (!p || (n && fread(p, sizeof(T), n, f) != n)) *ok = false;
-    return p;
-}
 
 bool read_scene(const char* path, Scene& s) {
     FILE* f = fopen(path, "rb");
@@ -81,32 +61,6 @@ struct Outputs {
     std::vector<int> position, counts;
 };
 
-template <class T>
-void fill_vector(std::vector<T>& v, size_t n, int fill) {
-    v.assign(n + 1, T());  // one spare element: data() is never null
-    memset(v.data(), fill, (n + 1) * sizeof(T));
-    v.resize(n);
-}
-
-void exclusive_scan(long long* val, long long n) {
-    long long run = 0;
-    for (long long i = 0; i < n; ++i) {
-        const long long x = val[i];
-        val[i] = run;
-        run += x;
-    }
-    val[n] = run;
-}
-
-template <class F>
-void walk(long long n, bool descending, F f) {
-    if (descending) {
-        for (long long i = n - 1; i >= 0; --i) f(i);
-    } else {
-        for (long long i = 0; i < n; ++i) f(i);
-    }
-}
-
 // 0: done; 3: refused
 int run(const Scene& s, bool descending, int lanes, int fill, Outputs& out) {
     const long long E = s.E, S = s.S, N = s.N, T = s.T, D = s.D, rows = E + S, nodes = N + T;
@@ -126,8 +80,7 @@ int run(const Scene& s, bool descending, int lanes, int fill, Outputs& out) {
         return 3;
     }
     const size_t bytes = tr_layout(nullptr, rows, nodes, D, nodes, 0).bytes;  // lds_node_limit 0: the state slices exist
-    void* ws = aligned_alloc(256, align_up(bytes ? bytes : 1, 256));
-    memset(ws, fill, align_up(bytes ? bytes : 1, 256));
+    void* ws = filled(bytes, fill);
     TrGraph g{s.pair_images, s.pair_direction, s.has_pair_enable ? s.pair_enable : nullptr, s.rotation, s.rotation_valid, s.intrinsics, s.track_off, s.image, s.uv,
               s.track_enable, s.has_meas_enable ? s.meas_enable : nullptr, s.directions, E, S, T, D, (int)N, s.directions_given ? 1 : 0, out.world_pair.data(),
               out.world_meas.data(), tr_layout(ws, rows, nodes, D, nodes, 0)};
@@ -177,19 +130,9 @@ int run(const Scene& s, bool descending, int lanes, int fill, Outputs& out) {
     return 0;
 }
 
-template <class T>
-bool write_vector(FILE* f, const std::vector<T>& v) {
-    return v.empty() || fwrite(v.data(), sizeof(T), v.size(), f) == v.size();
-}
-
 bool write_outputs(FILE* f, const Outputs& o) {
     return write_vector(f, o.world_pair) && write_vector(f, o.world_meas) && write_vector(f, o.pair_weight) && write_vector(f, o.meas_weight) &&
            write_vector(f, o.pair_inlier) && write_vector(f, o.meas_inlier) && write_vector(f, o.camera_inlier) && write_vector(f, o.position) && write_vector(f, o.counts);
-}
-
-template <class T>
-bool same(const std::vector<T>& a, const std::vector<T>& b) {
-    return a.size() == b.size() && (a.empty() || memcmp(a.data(), b.data(), a.size() * sizeof(T)) == 0);
 }
 
 }  // namespace

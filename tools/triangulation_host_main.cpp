@@ -15,21 +15,8 @@
 // status 2 when they are not, 3 / 4 for the two error flags of the device call (nothing written), 1 for a bad file. Every input array
 // is a heap allocation of its exact size, so a read outside it is a sanitizer report.
 
-#include <stdarg.h>
-#include <stdlib.h>
-#include <string.h>
-
-#include <vector>
-
 #include "../gtsfm_amd/csrc/triangulation_kernels.hip"
-
-void gtsfm_set_error(const char* fmt, ...) {
-    va_list args;
-    va_start(args, fmt);
-    vfprintf(stderr, fmt, args);
-    va_end(args);
-    fputc('\n', stderr);
-}
+#include "host_main_common.h"
 
 namespace {
 
@@ -44,16 +31,6 @@ struct Scene {
     float* uv;
     double* cams;
 };
-
-template <class T>
-T* read_array(FILE* f, size_t n) {
-    T* p = (T*)malloc(n ? n * sizeof(T) : 1);  // exact size: the sanitizer sees every read past the end
-    if (p && n && fread(p, sizeof(T), n, f) != n) {
-        free(p);
-        return nullptr;
-    }
-    return p;
-}
 
 bool read_scene(const char* path, Scene& s) {
     FILE* f = fopen(path, "rb");
@@ -71,11 +48,10 @@ bool read_scene(const char* path, Scene& s) {
         s.seed = (unsigned long long)head[6];
         s.threshold = opts[0];
         s.min_angle = opts[1];
-        s.track_off = read_array<long long>(f, (size_t)s.num_tracks + 1);
-        s.image = read_array<int>(f, (size_t)s.total);
-        s.uv = read_array<float>(f, 2 * (size_t)s.total);
-        s.cams = read_array<double>(f, 17 * (size_t)s.num_images);
-        ok = s.track_off && s.image && s.uv && s.cams;
+        s.track_off = read_array<long long>(f, (size_t)s.num_tracks + 1, &ok);
+        s.image = read_array<int>(f, (size_t)s.total, &ok);
+        s.uv = read_array<float>(f, 2 * (size_t)s.total, &ok);
+        s.cams = read_array<double>(f, 17 * (size_t)s.num_images, &ok);
     }
     fclose(f);
     return ok;
@@ -104,20 +80,13 @@ int run(const Scene& s, bool device_partition, Outputs& out) {
     const int mode = (int)s.mode;
     const long long max_hyp = mode == TRI_NO_RANSAC ? 0 : s.num_hyp;
     const size_t bytes = tri_layout(nullptr, s.num_tracks, s.total, max_hyp).bytes;
-    void* base = aligned_alloc(256, bytes);
+    void* base = filled(bytes, device_partition ? 0xFF : 0x00);
     if (!base) return 1;
-    memset(base, device_partition ? 0xFF : 0x00, bytes);
     const TriWorkspace w = tri_layout(base, s.num_tracks, s.total, max_hyp);
     memset(w.flags, 0, 16);
     for (long long t = 0; t < s.num_tracks; ++t) tri_count_track(t, s.track_off, s.num_tracks, s.total, mode, max_hyp, w.hyp_off, w.flags);
-    long long carry = 0;
-    for (long long t = 0; t < s.num_tracks; ++t) {  // the scan kernel, serially
-        const long long x = w.hyp_off[t];
-        w.hyp_off[t] = carry;
-        carry += x;
-    }
-    w.hyp_off[s.num_tracks] = carry;
-    if (carry > w.cap) w.flags[1] = 1;
+    exclusive_scan(w.hyp_off, s.num_tracks);  // the scan kernel, serially
+    if (w.hyp_off[s.num_tracks] > w.cap) w.flags[1] = 1;
     if (mode != TRI_NO_RANSAC) {
         const int select_lanes = device_partition ? TRI_THREADS : 1;
         for (long long t = 0; t < s.num_tracks; ++t)

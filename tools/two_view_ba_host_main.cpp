@@ -27,22 +27,9 @@
 // within 0 .. M; 1: a bad file.
 // Every input array is a heap allocation of its exact size, so a read outside it is a sanitizer report.
 
-#include <stdarg.h>
-#include <stdlib.h>
-#include <string.h>
-
-#include <vector>
-
 #include "../gtsfm_amd/csrc/triangulation_kernels.hip"
 #include "../gtsfm_amd/csrc/two_view_ba_kernels.hip"
-
-void gtsfm_set_error(const char* fmt, ...) {
-    va_list args;
-    va_start(args, fmt);
-    vfprintf(stderr, fmt, args);
-    va_end(args);
-    fputc('\n', stderr);
-}
+#include "host_main_common.h"
 
 namespace {
 
@@ -58,16 +45,6 @@ struct Scene {
     double *intrinsics, *rotation, *translation;
 };
 
-template <class T>
-T* read_array(FILE* f, size_t n) {
-    T* p = (T*)malloc(n ? n * sizeof(T) : 1);  // exact size: the sanitizer sees every read past the end
-    if (p && n && fread(p, sizeof(T), n, f) != n) {
-        free(p);
-        return nullptr;
-    }
-    return p;
-}
-
 bool read_scene(const char* path, Scene& s) {
     FILE* f = fopen(path, "rb");
     if (!f) return false;
@@ -80,17 +57,16 @@ bool read_scene(const char* path, Scene& s) {
         s.has_count = head[7];
         s.reproj = opts[0], s.huber_k = opts[1], s.sigma = opts[2], s.pose_sigma = opts[3], s.point_sigma = opts[4], s.tri_threshold = opts[5], s.tri_angle = opts[6];
         const size_t p = (size_t)s.num_pairs, m = (size_t)s.total;
-        s.kp_xy = read_array<float>(f, 2 * (size_t)s.kp_rows);
-        s.kp_off1 = read_array<long long>(f, p);
-        s.kp_off2 = read_array<long long>(f, p);
-        s.match_idx = read_array<int>(f, 2 * m);
-        s.match_off = read_array<long long>(f, p + 1);
-        s.match_count = read_array<int>(f, p);
-        s.inlier_mask = read_array<uint8_t>(f, m);
-        s.intrinsics = read_array<double>(f, 8 * p);
-        s.rotation = read_array<double>(f, 9 * p);
-        s.translation = read_array<double>(f, 3 * p);
-        ok = s.kp_xy && s.kp_off1 && s.kp_off2 && s.match_idx && s.match_off && s.match_count && s.inlier_mask && s.intrinsics && s.rotation && s.translation;
+        s.kp_xy = read_array<float>(f, 2 * (size_t)s.kp_rows, &ok);
+        s.kp_off1 = read_array<long long>(f, p, &ok);
+        s.kp_off2 = read_array<long long>(f, p, &ok);
+        s.match_idx = read_array<int>(f, 2 * m, &ok);
+        s.match_off = read_array<long long>(f, p + 1, &ok);
+        s.match_count = read_array<int>(f, p, &ok);
+        s.inlier_mask = read_array<uint8_t>(f, m, &ok);
+        s.intrinsics = read_array<double>(f, 8 * p, &ok);
+        s.rotation = read_array<double>(f, 9 * p, &ok);
+        s.translation = read_array<double>(f, 3 * p, &ok);
     }
     fclose(f);
     return ok;
@@ -306,9 +282,8 @@ void adjust_pair(const Scene& s, const TvbaWorkspace& w, int p, bool device_part
 // 0, or the error flag's exit status
 int run(const Scene& s, bool second, Outputs& out, FILE* trace) {
     const size_t bytes = tvba_layout(nullptr, s.num_pairs, s.total).bytes;
-    void* base = aligned_alloc(256, bytes);
+    void* base = filled(bytes, second ? 0xFF : 0x00);
     if (!base) return 1;
-    memset(base, second ? 0xFF : 0x00, bytes);
     const TvbaWorkspace w = tvba_layout(base, s.num_pairs, s.total);
     memset(w.flags, 0, 16);
     const int lanes = second ? TVBA_THREADS : 1;

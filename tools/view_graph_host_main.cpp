@@ -1,4 +1,4 @@
-// Stand-alone host build of the view-graph kernels' per-index functions (the VG_HD functions of gtsfm_amd/csrc/view_graph_kernels.hip: the
+// Stand-alone host build of the view-graph kernels' per-index functions (the GTSFM_HD functions of gtsfm_amd/csrc/view_graph_kernels.hip: the
 // adjacency, the merge of two neighbour lists, the cycle error, the per-edge aggregate, the component labelling), for running them on a CPU
 // and under the host sanitizers:
 //
@@ -20,21 +20,8 @@
 // with the reason on stderr; 1: a bad file.
 // Every input array is a heap allocation of its exact size, so a read outside it is a sanitizer report.
 
-#include <stdarg.h>
-#include <stdlib.h>
-#include <string.h>
-
-#include <vector>
-
 #include "../gtsfm_amd/csrc/view_graph_kernels.hip"
-
-void gtsfm_set_error(const char* fmt, ...) {
-    va_list args;
-    va_start(args, fmt);
-    vfprintf(stderr, fmt, args);
-    va_end(args);
-    fputc('\n', stderr);
-}
+#include "host_main_common.h"
 
 namespace {
 
@@ -48,16 +35,6 @@ struct Scene {
     uint8_t* enable;
 };
 
-template <class T>
-T* read_array(FILE* f, size_t n) {
-    T* p = (T*)malloc(n ? n * sizeof(T) : 1);  // exact size: the sanitizer sees every read past the end
-    if (p && n && fread(p, sizeof(T), n, f) != n) {
-        free(p);
-        return nullptr;
-    }
-    return p;
-}
-
 bool read_scene(const char* path, Scene& s) {
     FILE* f = fopen(path, "rb");
     if (!f) return false;
@@ -67,10 +44,9 @@ bool read_scene(const char* path, Scene& s) {
               head[2] < VG_MAX_IMAGES && (head[4] == 0 || head[4] == 1);
     if (ok) {
         s.num_edges = head[1], s.num_images = head[2], s.has_enable = head[3], s.criterion = head[4], s.threshold = opts[0];
-        s.pair_images = read_array<int>(f, 2 * (size_t)s.num_edges);
-        s.rotation = read_array<double>(f, 9 * (size_t)s.num_edges);
-        s.enable = read_array<uint8_t>(f, (size_t)s.num_edges);
-        ok = s.pair_images && s.rotation && s.enable;
+        s.pair_images = read_array<int>(f, 2 * (size_t)s.num_edges, &ok);
+        s.rotation = read_array<double>(f, 9 * (size_t)s.num_edges, &ok);
+        s.enable = read_array<uint8_t>(f, (size_t)s.num_edges, &ok);
     }
     fclose(f);
     return ok;
@@ -82,38 +58,6 @@ struct Outputs {
     std::vector<uint8_t> keep, node_mask, pair_keep;
     long long total = 0;
 };
-
-void* filled(size_t bytes, int fill) {
-    void* p = aligned_alloc(256, align_up(bytes ? bytes : 1, 256));
-    if (p) memset(p, fill, align_up(bytes ? bytes : 1, 256));
-    return p;
-}
-
-template <class T>
-void fill_vector(std::vector<T>& v, size_t n, int fill) {
-    v.resize(n);
-    if (n) memset(v.data(), fill, n * sizeof(T));
-}
-
-void exclusive_scan(long long* val, long long n) {
-    long long run = 0;
-    for (long long i = 0; i < n; ++i) {
-        const long long x = val[i];
-        val[i] = run;
-        run += x;
-    }
-    val[n] = run;
-}
-
-// f(i) for i in 0 .. n - 1, ascending or descending
-template <class F>
-void walk(long long n, bool descending, F f) {
-    if (descending) {
-        for (long long i = n - 1; i >= 0; --i) f(i);
-    } else {
-        for (long long i = 0; i < n; ++i) f(i);
-    }
-}
 
 // 0: done; 3: refused
 int run(const Scene& s, bool descending, int fill, Outputs& out) {
@@ -178,13 +122,13 @@ int run(const Scene& s, bool descending, int fill, Outputs& out) {
     const long long init_n = N > VG_FLAG_WORDS ? N : VG_FLAG_WORDS;
     walk(init_n, descending, [&](long long i) { vg_cc_init(c, i); });
     for (int rounds = 0; E > 0;) {
-        if (rounds == VG_MAX_ROUNDS) {
+        if (rounds == UF_MAX_ROUNDS) {
             fprintf(stderr, "refused: no fixed point after %d rounds\n", rounds);
             free(ws);
             return 3;
         }
         walk(E, descending, [&](long long i) { vg_cc_hook(c, i, rounds); });
-        walk(N, descending, [&](long long i) { vg_cc_compress(c, i); });
+        walk(N, descending, [&](long long i) { uf_compress(c.parent, c.label, i); });
         if (c.flags[0]) {
             fprintf(stderr, "refused: a bad pair\n");
             free(ws);
@@ -216,20 +160,10 @@ int run(const Scene& s, bool descending, int fill, Outputs& out) {
     return 0;
 }
 
-template <class T>
-bool write_vector(FILE* f, const std::vector<T>& v) {
-    return v.empty() || fwrite(v.data(), sizeof(T), v.size(), f) == v.size();
-}
-
 bool write_outputs(FILE* f, const Outputs& o) {
     return write_vector(f, o.num_triplets) && write_vector(f, o.aggregate) && write_vector(f, o.keep) && write_vector(f, o.counts) && fwrite(&o.total, 8, 1, f) == 1 &&
            write_vector(f, o.triplets) && write_vector(f, o.cycle_error) && write_vector(f, o.node_mask) && write_vector(f, o.pair_keep) &&
            write_vector(f, o.component_counts);
-}
-
-template <class T>
-bool same(const std::vector<T>& a, const std::vector<T>& b) {
-    return a.size() == b.size() && (a.empty() || memcmp(a.data(), b.data(), a.size() * sizeof(T)) == 0);
 }
 
 }  // namespace
