@@ -38,17 +38,19 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 __host__ __device__ static inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
 static inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
+static inline size_t a64(size_t floats) { return align_up(floats, 64); }  // pieces of a packed weight blob start at multiples of 64 floats
 
 // Lays a workspace out: consecutive pieces, each starting at a multiple of 256 bytes from `base`. A size query passes a null base and
-// reads `used`.
+// reads `used`; a layout that keeps offsets takes them with offset().
 struct WorkspaceCarver {
     void* base;
     size_t used;
-    void* take(size_t bytes) {
+    size_t offset(size_t bytes) {
         const size_t at = used;
         used += align_up(bytes, 256);
-        return (void*)((uintptr_t)base + at);
+        return at;
     }
+    void* take(size_t bytes) { return (void*)((uintptr_t)base + offset(bytes)); }
 };
 
 // Wave-wide reductions over all 64 lanes (result valid in every lane).

@@ -3,7 +3,7 @@
 // See include/gtsfm_amd.h.
 //
 // Forward (all exact fp32, NHWC activations, 64-bit offsets):
-//   1. d2_conv1_kernel   : conv1_1 (3 -> 64) + ReLU on the VALU. A uint8 pixel is normalised through a 3 x 256 table the host built with
+//   1. vgg_conv1_kernel<D2Load> (vgg_trunk.h, shared with NetVLAD): conv1_1 (3 -> 64) + ReLU on the VALU. A uint8 pixel is normalised through a 3 x 256 table the host built with
 //                          the reference's own expression (utils.py:23-38 in float64, rounded to float32), so the input equals the
 //                          reference's bit for bit; a float image arrives normalised. Zero padding applies to the normalised image.
 //   2. conv1_2 .. conv3_3: launch_conv3x3 (dense_kernels.hip), ReLU after every layer, max-pool fused after conv1_2 and conv2_2.
@@ -23,16 +23,14 @@
 #include "../../include/gtsfm_amd.h"
 #include "common.h"
 #include "conv_kernels.h"
+#include "vgg_trunk.h"
 
-#define D2_LAYERS 10
+#define D2_LAYERS 10  // the trunk up to conv4_3
 #define D2_C 512
-#define D2_C1_T 16  // conv1_1 output tile: 16 x 16 pixels
 #define D2_LUT 768  // 3 x 256
 
 namespace {
 
-const int kCin[D2_LAYERS] = {3, 64, 64, 128, 128, 256, 256, 256, 512, 512};
-const int kCout[D2_LAYERS] = {64, 64, 128, 128, 256, 256, 256, 512, 512, 512};
 const int kPool[D2_LAYERS] = {0, 1, 0, 1, 0, 0, 0, 0, 0, 0};
 const int kFirstDilated = 7;  // the average pool sits in front of it
 
@@ -42,22 +40,14 @@ struct D2Cand {
 };
 static_assert(sizeof(D2Cand) == 24, "candidate records are six 32-bit words");
 
-size_t a64(size_t floats) { return align_up(floats, 64); }
-
-// Offsets (floats) of the packed blob: conv1_1 raw [64][27] + bias, conv1_2 .. conv4_3 packed (pack_conv3x3_weights) + bias, table [3][256].
+// Offsets (floats) of the packed blob: the 10 convolutions (vgg_conv_layout), table [3][256].
 struct D2Layout {
     size_t w[D2_LAYERS], b[D2_LAYERS], lut, total;
 };
 
 D2Layout d2_layout() {
     D2Layout L;
-    size_t o = 0;
-    for (int l = 0; l < D2_LAYERS; ++l) {
-        L.w[l] = o;
-        o += a64(l == 0 ? (size_t)64 * 27 : packed_conv3x3_floats(kCin[l], kCout[l]));
-        L.b[l] = o;
-        o += a64(kCout[l]);
-    }
+    size_t o = vgg_conv_layout(D2_LAYERS, L.w, L.b);
     L.lut = o, o += D2_LUT;
     L.total = o;
     return L;
@@ -70,11 +60,11 @@ struct D2DetWs {
 
 D2DetWs d2_det_ws(int B, int cap) {
     D2DetWs s;
-    size_t o = 0;
-    s.counts = o, o += align_up((size_t)B * 4, 256);
-    s.cand = o, o += align_up((size_t)B * cap * sizeof(D2Cand), 256);
-    s.sorted = o, o += align_up((size_t)B * cap * sizeof(D2Cand), 256);
-    s.total = o;
+    WorkspaceCarver c = {};
+    s.counts = c.offset((size_t)B * 4);
+    s.cand = c.offset((size_t)B * cap * sizeof(D2Cand));
+    s.sorted = c.offset((size_t)B * cap * sizeof(D2Cand));
+    s.total = c.used;
     return s;
 }
 
@@ -85,78 +75,26 @@ struct D2Ws {
 
 D2Ws d2_ws(int B, int H, int W, int cap) {
     D2Ws s;
-    const size_t act = align_up((size_t)B * H * W * 64 * 4, 256);
-    size_t o = 0;
-    s.actA = o, o += act;
-    s.actB = o, o += act;
-    s.det = o, o += d2_det_ws(B, cap).total;
-    s.total = o;
+    WorkspaceCarver c = {};
+    s.actA = c.offset((size_t)B * H * W * 64 * 4);
+    s.actB = c.offset((size_t)B * H * W * 64 * 4);
+    s.det = c.offset(d2_det_ws(B, cap).total);
+    s.total = c.used;
     return s;
 }
 
-// ------------------------------------------------------------------------------------------------------------------------------
-// conv1_1 with the preprocessing (nv_conv1_kernel's scheme). One thread per output pixel, 64 output channels in registers; weights as
-// [27 taps][64] in LDS, the normalised 3 x 18 x 18 input patch in LDS (zero outside the image). acc = bias, then fmaf over the taps in
-// torch's (c, ky, kx) order. layout 0: float [B][3][H][W] normalised; 1: uint8 [B][H][W][3]; 2: uint8 [B][H][W] (gray = three equal channels).
-// ------------------------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void d2_conv1_kernel(const void* __restrict__ img, int layout, int H, int W, int tiles_x, int tiles_y,
-                                                     const float* __restrict__ w1, const float* __restrict__ b1, const float* __restrict__ lut,
-                                                     float* __restrict__ out) {
-    __shared__ __attribute__((aligned(16))) float wt[27 * 64];
-    __shared__ float patch[3][D2_C1_T + 2][D2_C1_T + 2];
-    const int tid = threadIdx.x;
-    int bid = blockIdx.x;
-    const int tx = bid % tiles_x;
-    bid /= tiles_x;
-    const int ty = bid % tiles_y;
-    const size_t b = bid / tiles_y;
-    const int x0 = tx * D2_C1_T, y0 = ty * D2_C1_T;
-    for (int idx = tid; idx < 27 * 64; idx += 256) {
-        const int tap = idx >> 6, o = idx & 63;
-        wt[idx] = w1[o * 27 + tap];
+// conv1_1's pixel fetch (vgg_conv1_kernel): the normalised value. layout 0: float [B][3][H][W], normalised already; 1: uint8 [B][H][W][3]
+// and 2: uint8 [B][H][W] (gray = three equal channels) through the table.
+struct D2Load {
+    const void* img;
+    int layout;
+    const float* lut;
+    __device__ float operator()(size_t b, int c, int gy, int gx, int H, int W) const {
+        if (layout == 0) return reinterpret_cast<const float*>(img)[((b * 3 + c) * H + gy) * (size_t)W + gx];
+        if (layout == 1) return lut[c * 256 + reinterpret_cast<const uint8_t*>(img)[((b * H + gy) * W + gx) * 3 + c]];
+        return lut[c * 256 + reinterpret_cast<const uint8_t*>(img)[(b * H + gy) * W + gx]];
     }
-    for (int idx = tid; idx < 3 * (D2_C1_T + 2) * (D2_C1_T + 2); idx += 256) {
-        const int c = idx / ((D2_C1_T + 2) * (D2_C1_T + 2)), r = idx % ((D2_C1_T + 2) * (D2_C1_T + 2));
-        const int py = r / (D2_C1_T + 2), px = r % (D2_C1_T + 2);
-        const int gy = y0 - 1 + py, gx = x0 - 1 + px;
-        float v = 0.f;
-        if (gy >= 0 && gy < H && gx >= 0 && gx < W) {
-            if (layout == 0)
-                v = reinterpret_cast<const float*>(img)[((b * 3 + c) * H + gy) * (size_t)W + gx];
-            else if (layout == 1)
-                v = lut[c * 256 + reinterpret_cast<const uint8_t*>(img)[((b * H + gy) * W + gx) * 3 + c]];
-            else
-                v = lut[c * 256 + reinterpret_cast<const uint8_t*>(img)[(b * H + gy) * W + gx]];
-        }
-        patch[c][py][px] = v;
-    }
-    __syncthreads();
-    const int px = tid & 15, py = tid >> 4;
-    float acc[64];
-#pragma unroll
-    for (int o = 0; o < 64; ++o) acc[o] = b1[o];
-    for (int c = 0; c < 3; ++c)
-#pragma unroll
-        for (int t = 0; t < 9; ++t) {
-            const float v = patch[c][py + t / 3][px + t % 3];
-            const f32x4* wrow = reinterpret_cast<const f32x4*>(wt + (c * 9 + t) * 64);
-#pragma unroll
-            for (int q = 0; q < 16; ++q) {
-                const f32x4 w = wrow[q];
-                acc[4 * q] = fmaf(w[0], v, acc[4 * q]);
-                acc[4 * q + 1] = fmaf(w[1], v, acc[4 * q + 1]);
-                acc[4 * q + 2] = fmaf(w[2], v, acc[4 * q + 2]);
-                acc[4 * q + 3] = fmaf(w[3], v, acc[4 * q + 3]);
-            }
-        }
-    const int y = y0 + py, x = x0 + px;
-    if (y < H && x < W) {
-        f32x4* dst = reinterpret_cast<f32x4*>(out + ((b * H + y) * W + x) * 64);
-#pragma unroll
-        for (int q = 0; q < 16; ++q)
-            dst[q] = f32x4{fmaxf(acc[4 * q], 0.f), fmaxf(acc[4 * q + 1], 0.f), fmaxf(acc[4 * q + 2], 0.f), fmaxf(acc[4 * q + 3], 0.f)};
-    }
-}
+};
 
 // AvgPool2d(2, stride 1) on [B][h][w][C] -> [B][h - 1][w - 1][C], one thread per four channels of an output pixel.
 __global__ __launch_bounds__(256) void d2_avgpool_kernel(const float* __restrict__ in, int h, int w, int c4, size_t total, float* __restrict__ out) {
@@ -372,12 +310,8 @@ int d2_run(const float* wts, const void* image, int layout, int B, int H, int W,
     const D2Layout L = d2_layout();
     char* base = reinterpret_cast<char*>(ws);
     float* act[2] = {reinterpret_cast<float*>(base + s.actA), reinterpret_cast<float*>(base + s.actB)};
-    {
-        const int tx = ceil_div(W, D2_C1_T), ty = ceil_div(H, D2_C1_T);
-        hipLaunchKernelGGL(d2_conv1_kernel, dim3((unsigned)B * tx * ty), dim3(256), 0, st, image, layout, H, W, tx, ty, wts + L.w[0], wts + L.b[0],
-                           wts + L.lut, act[0]);
-        GTSFM_CHECK_LAUNCH("d2_conv1_kernel");
-    }
+    vgg_launch_conv1(D2Load{image, layout, wts + L.lut}, B, H, W, wts + L.w[0], wts + L.b[0], act[0], st);
+    GTSFM_CHECK_LAUNCH("vgg_conv1_kernel<D2Load>");
     if (stage == 0) return d2_copy_out(out, act[0], (size_t)B * H * W * 64, st);
     int h = H, w = W, cur = 0;
     for (int l = 1; l < D2_LAYERS; ++l) {
@@ -388,13 +322,7 @@ int d2_run(const float* wts, const void* image, int layout, int B, int H, int W,
             GTSFM_CHECK_LAUNCH("d2_avgpool_kernel");
             cur ^= 1, --h, --w;
         }
-        ConvParams p = {};
-        p.in = act[cur], p.in_stride = kCin[l], p.in_coff = 0;
-        p.out = act[cur ^ 1], p.out_stride = kCout[l], p.out_coff = 0;
-        p.wpack = wts + L.w[l], p.bias = wts + L.b[l];
-        p.B = B, p.H = h, p.W = w, p.Cin = kCin[l], p.Cout = kCout[l];
-        p.relu = 1, p.pool = kPool[l];
-        const int rc = l >= kFirstDilated ? launch_conv3x3_dil2(p, st) : launch_conv3x3(p, st);
+        const int rc = vgg_conv_layer(l, act[cur], act[cur ^ 1], wts + L.w[l], wts + L.b[l], B, h, w, 1, kPool[l], l >= kFirstDilated, st);
         if (rc) return rc;
         cur ^= 1;
         if (kPool[l]) h >>= 1, w >>= 1;
@@ -430,13 +358,7 @@ int gtsfm_d2net_pack_weights(const float* const* t, float* packed) {
     for (int i = 0; i < 2 * D2_LAYERS + 1; ++i) GTSFM_CHECK_ARG(t[i], "d2net_pack_weights: tensor %d is null", i);
     const D2Layout L = d2_layout();
     for (size_t i = 0; i < L.total; ++i) packed[i] = 0.f;
-    for (int l = 0; l < D2_LAYERS; ++l) {
-        if (l == 0)
-            for (int i = 0; i < 64 * 27; ++i) packed[L.w[0] + i] = t[0][i];
-        else
-            pack_conv3x3_weights(t[2 * l], kCin[l], kCout[l], packed + L.w[l]);
-        for (int o = 0; o < kCout[l]; ++o) packed[L.b[l] + o] = t[2 * l + 1][o];
-    }
+    vgg_pack_convs(t, D2_LAYERS, L.w, L.b, packed);
     for (int i = 0; i < D2_LUT; ++i) packed[L.lut + i] = t[2 * D2_LAYERS][i];
     return GTSFM_OK;
 }

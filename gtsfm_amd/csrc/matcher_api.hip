@@ -282,31 +282,26 @@ struct SgWorkspace {
 
 SgWorkspace sg_workspace_layout(const BatchDims& d, int attn_math) {
     SgWorkspace w;
-    size_t o = 0;
-    auto take = [&](size_t floats) {
-        size_t r = o;
-        o += align_up(floats * 4, 256);
-        return r;
-    };
-    const size_t T = d.T;
-    w.enc_in = take(T * 8);
-    w.ka = take(T * 256);
-    w.kb = take(T * 256);
-    w.x = take(T * 512);
-    w.qkv = take(T * 768);
-    w.mlp = take(T * 512);
-    w.md = take(T * 256);
-    w.pack = take(d.pack_floats);
-    w.z = take(d.z_floats);
-    w.part = take(d.part_floats);
-    w.uv_row = take(T + 16 * d.P + 8);
-    w.uv_col = take(T + 16 * d.P + 8);
-    w.max0 = take(T);
-    w.idx0 = take(T);
-    w.idx1 = take(T);
+    WorkspaceCarver c = {};
+    const size_t T = d.T, F = sizeof(float);
+    w.enc_in = c.offset(T * 8 * F);
+    w.ka = c.offset(T * 256 * F);
+    w.kb = c.offset(T * 256 * F);
+    w.x = c.offset(T * 512 * F);
+    w.qkv = c.offset(T * 768 * F);
+    w.mlp = c.offset(T * 512 * F);
+    w.md = c.offset(T * 256 * F);
+    w.pack = c.offset(d.pack_floats * F);
+    w.z = c.offset(d.z_floats * F);
+    w.part = c.offset(d.part_floats * F);
+    w.uv_row = c.offset((T + 16 * d.P + 8) * F);
+    w.uv_col = c.offset((T + 16 * d.P + 8) * F);
+    w.max0 = c.offset(T * F);
+    w.idx0 = c.offset(T * F);
+    w.idx1 = c.offset(T * F);
     w.attn_floats = attention_workspace_floats(2 * d.P, 4, d.max_n, d.max_n, T, attn_math);  // split partials (small batches) or fused parking space; 0 below 1025 keypoints
-    w.attn = take(w.attn_floats);
-    w.total = o;
+    w.attn = c.offset(w.attn_floats * F);
+    w.total = c.used;
     return w;
 }
 
@@ -479,17 +474,12 @@ struct SkWorkspace {
 SkWorkspace sk_workspace_layout(int P, const int32_t* m, const int32_t* n) {
     const BatchDims d = batch_dims(P, m, n, 1);
     SkWorkspace w;
-    size_t o = 0;
-    auto take = [&](size_t bytes) {
-        size_t r = o;
-        o += align_up(bytes, 256);
-        return r;
-    };
-    w.desc = take(desc_layout(P, 0).total * sizeof(int32_t));
-    w.part = take(d.part_floats * 4);
-    w.uv_row = take(((size_t)d.T + 16 * P + 8) * 4);
-    w.uv_col = take(((size_t)d.T + 16 * P + 8) * 4);
-    w.total = o;
+    WorkspaceCarver c = {};
+    w.desc = c.offset(desc_layout(P, 0).total * sizeof(int32_t));
+    w.part = c.offset(d.part_floats * 4);
+    w.uv_row = c.offset(((size_t)d.T + 16 * P + 8) * 4);
+    w.uv_col = c.offset(((size_t)d.T + 16 * P + 8) * 4);
+    w.total = c.used;
     return w;
 }
 
@@ -587,12 +577,7 @@ struct LgaWorkspace {
 
 LgaWorkspace lga_workspace_layout(int P, const int32_t* m, const int32_t* n) {
     LgaWorkspace w;
-    size_t o = 0;
-    auto take = [&](size_t bytes) {
-        size_t r = o;
-        o += align_up(bytes, 256);
-        return r;
-    };
+    WorkspaceCarver c = {};
     size_t Tp = 0, part = 0;
     int mx = 0;
     for (int p = 0; p < P; ++p) mx = mx > n[p] ? mx : n[p];
@@ -601,11 +586,11 @@ LgaWorkspace lga_workspace_layout(int P, const int32_t* m, const int32_t* n) {
         Tp += (size_t)cap128(m[p]) + cap128(n[p]);
         part += (size_t)ceil_div(m[p], R) * z_ld(n[p], 0) * 2;
     }
-    w.desc = take(desc_layout(P, count_tiles(0, P, m, n)).total * sizeof(int32_t));
-    w.part = take(part * 4);
-    w.uv_row = take((Tp + 16 * (size_t)P + 8) * 4), w.uv_col = take((Tp + 16 * (size_t)P + 8) * 4);
-    w.max0 = take(Tp * 4), w.idx0 = take(Tp * 4), w.idx1 = take(Tp * 4);
-    w.total = o;
+    w.desc = c.offset(desc_layout(P, count_tiles(0, P, m, n)).total * sizeof(int32_t));
+    w.part = c.offset(part * 4);
+    w.uv_row = c.offset((Tp + 16 * (size_t)P + 8) * 4), w.uv_col = c.offset((Tp + 16 * (size_t)P + 8) * 4);
+    w.max0 = c.offset(Tp * 4), w.idx0 = c.offset(Tp * 4), w.idx1 = c.offset(Tp * 4);
+    w.total = c.used;
     return w;
 }
 
@@ -699,22 +684,17 @@ struct LgWorkspace {
 
 LgWorkspace lg_workspace_layout(const LgDims& d, int attn_math) {
     LgWorkspace w;
-    size_t o = 0;
-    auto take = [&](size_t floats) {
-        size_t r = o;
-        o += align_up(floats * 4, 256);
-        return r;
-    };
-    const size_t T = d.Tp;
-    w.xa = take(T * 512), w.xb = take(T * 512), w.qkv = take(T * 768), w.mlp = take(T * 512), w.md = take(T * 256);
-    w.enca = take(T * 64), w.encb = take(T * 64), w.inda = take(T), w.indb = take(T), w.indf = take(T);
-    w.conf = take(T), w.mval = take(T), w.z_logit = take(T), w.pos = take(T);
-    w.pack = take(d.pack_floats), w.z = take(d.z_floats), w.part = take(d.part_floats);
-    w.uv_row = take(T + 16 * d.P + 8), w.uv_col = take(T + 16 * d.P + 8);
-    w.max0 = take(T), w.idx0 = take(T), w.idx1 = take(T), w.m_int = take(T), w.ms_int = take(T);
+    WorkspaceCarver c = {};
+    const size_t T = d.Tp, F = sizeof(float);
+    w.xa = c.offset(T * 512 * F), w.xb = c.offset(T * 512 * F), w.qkv = c.offset(T * 768 * F), w.mlp = c.offset(T * 512 * F), w.md = c.offset(T * 256 * F);
+    w.enca = c.offset(T * 64 * F), w.encb = c.offset(T * 64 * F), w.inda = c.offset(T * F), w.indb = c.offset(T * F), w.indf = c.offset(T * F);
+    w.conf = c.offset(T * F), w.mval = c.offset(T * F), w.z_logit = c.offset(T * F), w.pos = c.offset(T * F);
+    w.pack = c.offset(d.pack_floats * F), w.z = c.offset(d.z_floats * F), w.part = c.offset(d.part_floats * F);
+    w.uv_row = c.offset((T + 16 * d.P + 8) * F), w.uv_col = c.offset((T + 16 * d.P + 8) * F);
+    w.max0 = c.offset(T * F), w.idx0 = c.offset(T * F), w.idx1 = c.offset(T * F), w.m_int = c.offset(T * F), w.ms_int = c.offset(T * F);
     w.attn_floats = attention_workspace_floats(2 * d.P, 4, d.max_n, d.max_n, T, attn_math);  // split partials (small batches) or fused parking space; 0 below 1025 keypoints
-    w.attn = take(w.attn_floats);
-    w.total = o;
+    w.attn = c.offset(w.attn_floats * F);
+    w.total = c.used;
     return w;
 }
 

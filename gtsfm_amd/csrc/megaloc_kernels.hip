@@ -48,8 +48,6 @@
 
 namespace {
 
-size_t a64(size_t floats) { return align_up(floats, 64); }
-
 struct MlBlock {
     size_t n1w, n1b, qkvw, qkvb, projw, projb, n2w, n2b, fc1w, fc1b, fc2w, fc2b;
 };
@@ -131,20 +129,21 @@ MlWs ml_ws(int B, int H, int W, int feat) {
     MlWs s;
     const int n = (H / ML_PATCH) * (W / ML_PATCH), T = n + 1, Bc = ml_chunk(B, T);
     const size_t R = (size_t)Bc * T;
-    size_t o = 256;
-    s.x = o, o += align_up(R * ML_D * 4, 256);
-    s.y = o, o += align_up(R * ML_D * 4, 256);
-    s.wide = o, o += align_up(R * ML_FF * 4, 256);
+    WorkspaceCarver c = {};
+    c.offset(4);  // the range flag of a call that passes none
+    s.x = c.offset(R * ML_D * 4);
+    s.y = c.offset(R * ML_D * 4);
+    s.wide = c.offset(R * ML_FF * 4);
     s.attn_floats = attention_workspace_floats(Bc, 4, T, T, R, ATTN_MATH_F32);
-    s.attn = o, o += align_up(s.attn_floats * 4, 256);
-    s.th = o, o += align_up((size_t)Bc * ML_MLP * 4, 256);
-    s.tk = o, o += align_up((size_t)Bc * ML_TOK * 4, 256);
-    s.vec = o, o += align_up((size_t)Bc * ML_SALAD * 4, 256);
-    s.part = o, o += align_up((size_t)ML_LIN_SLICES * Bc * feat * 4, 256);
-    s.problems = o, o += align_up((size_t)Bc * sizeof(AttnProblem), 256);
-    s.counts = o, o += 256;
-    s.mglob = o, o += ml_salad_lds_bytes(n, true) <= ML_LDS_LIMIT ? 0 : align_up((size_t)Bc * (ML_CL + 1) * n * 4, 256);
-    s.total = o;
+    s.attn = c.offset(s.attn_floats * 4);
+    s.th = c.offset((size_t)Bc * ML_MLP * 4);
+    s.tk = c.offset((size_t)Bc * ML_TOK * 4);
+    s.vec = c.offset((size_t)Bc * ML_SALAD * 4);
+    s.part = c.offset((size_t)ML_LIN_SLICES * Bc * feat * 4);
+    s.problems = c.offset((size_t)Bc * sizeof(AttnProblem));
+    s.counts = c.offset(256);
+    s.mglob = c.offset(ml_salad_lds_bytes(n, true) <= ML_LDS_LIMIT ? 0 : (size_t)Bc * (ML_CL + 1) * n * 4);
+    s.total = c.used;
     return s;
 }
 

@@ -3,8 +3,8 @@
 // See include/gtsfm_amd.h.
 //
 // Forward (all exact fp32):
-//   1. nv_conv1_kernel    : conv1_1 (3 -> 64) + ReLU on the VALU, with the reference's preprocessing applied while the input
-//                           tile is staged: clamp(x * 255, 0, 255) - mean[c] (netvlad.py:178-182; std = 1). Reads the plugin's
+//   1. vgg_conv1_kernel<NvLoad> (vgg_trunk.h, shared with D2-Net): conv1_1 (3 -> 64) + ReLU on the VALU, with the reference's
+//                           preprocessing applied while the input tile is staged: clamp(x * 255, 0, 255) - mean[c] (netvlad.py:178-182; std = 1). Reads the plugin's
 //                           [B][3][H][W] float image or a [B][H][W][3] uint8 one (float(u8) is what (u8 / 255) * 255 gives back).
 //                           Sets *range_flag when a float input lies outside [-1e-6, 1 + 1e-6] or is NaN (netvlad.py:177).
 //   2. conv1_2 .. conv5_3 : launch_conv3x3 (dense_kernels.hip), max-pool fused after conv1_2 / 2_2 / 3_3 / 4_3, no ReLU after conv5_3.
@@ -33,40 +33,30 @@
 #include "gemm_batch.h"
 #include "gemm_kernels.h"
 #include "splitk_linear.h"
+#include "vgg_trunk.h"
 
-#define NV_LAYERS 13
+#define NV_LAYERS VGG_LAYERS  // the whole trunk: conv1_1 .. conv5_3
 #define NV_D 512
 #define NV_K 64
 #define NV_VLAD (NV_D * NV_K)  // 32768
 #define NV_WHITE 4096
 #define NV_WSLICE 2048                 // depth of one whitening slice
 #define NV_WSPLIT (NV_VLAD / NV_WSLICE)  // 16
-#define NV_C1_T 16                     // conv1_1 output tile: 16 x 16 pixels
 #define RT_STRIP 1024                  // rows per retrieval GEMM problem
 
 namespace {
 
-const int kCin[NV_LAYERS] = {3, 64, 64, 128, 128, 256, 256, 256, 512, 512, 512, 512, 512};
-const int kCout[NV_LAYERS] = {64, 64, 128, 128, 256, 256, 256, 512, 512, 512, 512, 512, 512};
 const int kPool[NV_LAYERS] = {0, 1, 0, 1, 0, 0, 1, 0, 0, 1, 0, 0, 0};
 
-size_t a64(size_t floats) { return align_up(floats, 64); }
-
-// Offsets (floats) of the packed blob: conv1_1 raw [64][27] + bias, conv1_2 .. conv5_3 packed (pack_conv3x3_weights) + bias,
-// score_proj [64][512], centres [512][64], mean [4], then (with whitening) W [4096][32768] row-major and its bias.
+// Offsets (floats) of the packed blob: the 13 convolutions (vgg_conv_layout), score_proj [64][512], centres [512][64], mean [4], then
+// (with whitening) W [4096][32768] row-major and its bias.
 struct NvLayout {
     size_t w[NV_LAYERS], b[NV_LAYERS], score, centers, mean, ww, wb, total_plain, total_white;
 };
 
 NvLayout nv_layout() {
     NvLayout L;
-    size_t o = 0;
-    for (int l = 0; l < NV_LAYERS; ++l) {
-        L.w[l] = o;
-        o += a64(l == 0 ? (size_t)64 * 27 : packed_conv3x3_floats(kCin[l], kCout[l]));
-        L.b[l] = o;
-        o += a64(kCout[l]);
-    }
+    size_t o = vgg_conv_layout(NV_LAYERS, L.w, L.b);
     L.score = o, o += a64((size_t)NV_K * NV_D);
     L.centers = o, o += a64((size_t)NV_D * NV_K);
     L.mean = o, o += 64;
@@ -85,81 +75,32 @@ struct NvWs {
 NvWs nv_ws(int B, int H, int W) {
     NvWs s;
     const size_t hw = (size_t)H * W, hw5 = (size_t)(H / 16) * (W / 16);
-    size_t o = 256;
-    s.actA = o, o += align_up((size_t)B * hw * 64 * 4, 256);
-    s.actB = o, o += align_up((size_t)B * (hw / 4 + 1) * 64 * 4, 256);
-    s.scores = o, o += align_up((size_t)B * hw5 * NV_K * 4, 256);
-    s.vlad = o, o += align_up((size_t)B * NV_VLAD * 4, 256);
-    s.part = o, o += align_up((size_t)NV_WSPLIT * B * NV_WHITE * 4, 256);
-    s.total = o;
+    WorkspaceCarver c = {};
+    c.offset(4);  // the range flag of a call that passes none
+    s.actA = c.offset((size_t)B * hw * 64 * 4);
+    s.actB = c.offset((size_t)B * (hw / 4 + 1) * 64 * 4);
+    s.scores = c.offset((size_t)B * hw5 * NV_K * 4);
+    s.vlad = c.offset((size_t)B * NV_VLAD * 4);
+    s.part = c.offset((size_t)NV_WSPLIT * B * NV_WHITE * 4);
+    s.total = c.used;
     return s;
 }
 
-// ------------------------------------------------------------------------------------------------------------------------------
-// conv1_1 with the preprocessing. One thread per output pixel, 64 output channels in registers; weights as [27 taps][64] in LDS
-// (read as broadcast float4), the preprocessed 3 x 18 x 18 input patch in LDS (zero outside the image: the padding of conv1_1's
-// input, which is the mean-subtracted image). acc = bias, then fmaf over the taps in torch's (c, ky, kx) order.
-// ------------------------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void nv_conv1_kernel(const void* __restrict__ img, int u8, int H, int W, int tiles_x, int tiles_y,
-                                                     const float* __restrict__ w1, const float* __restrict__ b1, const float* __restrict__ mean,
-                                                     float* __restrict__ out, int* __restrict__ range_flag) {
-    __shared__ __attribute__((aligned(16))) float wt[27 * 64];
-    __shared__ float patch[3][NV_C1_T + 2][NV_C1_T + 2];
-    const int tid = threadIdx.x;
-    int bid = blockIdx.x;
-    const int tx = bid % tiles_x;
-    bid /= tiles_x;
-    const int ty = bid % tiles_y;
-    const size_t b = bid / tiles_y;
-    const int x0 = tx * NV_C1_T, y0 = ty * NV_C1_T;
-    for (int idx = tid; idx < 27 * 64; idx += 256) {
-        const int tap = idx >> 6, o = idx & 63;
-        wt[idx] = w1[o * 27 + tap];
+// conv1_1's pixel fetch (vgg_conv1_kernel) with the reference's preprocessing: clamp(x * 255, 0, 255) - mean[c] of a float image
+// [B][3][H][W], raising *range_flag when x lies outside [-1e-6, 1 + 1e-6] or is NaN; float(u8) - mean[c] of a uint8 image [B][H][W][3].
+struct NvLoad {
+    const void* img;
+    int u8;
+    const float* mean;
+    int* range_flag;
+    __device__ float operator()(size_t b, int c, int gy, int gx, int H, int W) const {
+        if (u8) return (float)reinterpret_cast<const uint8_t*>(img)[((b * H + gy) * W + gx) * 3 + c] - mean[c];
+        const float lo = (float)(-1e-6), hi = (float)(1.0 + 1e-6);
+        const float x = reinterpret_cast<const float*>(img)[((b * 3 + c) * H + gy) * (size_t)W + gx];
+        if (!(x >= lo && x <= hi)) atomicOr(range_flag, 1);
+        return fminf(fmaxf(x * 255.0f, 0.0f), 255.0f) - mean[c];
     }
-    const float lo = (float)(-1e-6), hi = (float)(1.0 + 1e-6);
-    for (int idx = tid; idx < 3 * (NV_C1_T + 2) * (NV_C1_T + 2); idx += 256) {
-        const int c = idx / ((NV_C1_T + 2) * (NV_C1_T + 2)), r = idx % ((NV_C1_T + 2) * (NV_C1_T + 2));
-        const int py = r / (NV_C1_T + 2), px = r % (NV_C1_T + 2);
-        const int gy = y0 - 1 + py, gx = x0 - 1 + px;
-        float v = 0.f;
-        if (gy >= 0 && gy < H && gx >= 0 && gx < W) {
-            if (u8) {
-                v = (float)reinterpret_cast<const uint8_t*>(img)[((b * H + gy) * W + gx) * 3 + c] - mean[c];
-            } else {
-                const float x = reinterpret_cast<const float*>(img)[((b * 3 + c) * H + gy) * (size_t)W + gx];
-                if (!(x >= lo && x <= hi)) atomicOr(range_flag, 1);
-                v = fminf(fmaxf(x * 255.0f, 0.0f), 255.0f) - mean[c];
-            }
-        }
-        patch[c][py][px] = v;
-    }
-    __syncthreads();
-    const int px = tid & 15, py = tid >> 4;
-    float acc[64];
-#pragma unroll
-    for (int o = 0; o < 64; ++o) acc[o] = b1[o];
-    for (int c = 0; c < 3; ++c)
-#pragma unroll
-        for (int t = 0; t < 9; ++t) {
-            const float v = patch[c][py + t / 3][px + t % 3];
-            const f32x4* wrow = reinterpret_cast<const f32x4*>(wt + (c * 9 + t) * 64);
-#pragma unroll
-            for (int q = 0; q < 16; ++q) {
-                const f32x4 w = wrow[q];
-                acc[4 * q] = fmaf(w[0], v, acc[4 * q]);
-                acc[4 * q + 1] = fmaf(w[1], v, acc[4 * q + 1]);
-                acc[4 * q + 2] = fmaf(w[2], v, acc[4 * q + 2]);
-                acc[4 * q + 3] = fmaf(w[3], v, acc[4 * q + 3]);
-            }
-        }
-    const int y = y0 + py, x = x0 + px;
-    if (y < H && x < W) {
-        f32x4* dst = reinterpret_cast<f32x4*>(out + ((b * H + y) * W + x) * 64);
-#pragma unroll
-        for (int q = 0; q < 16; ++q)
-            dst[q] = f32x4{fmaxf(acc[4 * q], 0.f), fmaxf(acc[4 * q + 1], 0.f), fmaxf(acc[4 * q + 2], 0.f), fmaxf(acc[4 * q + 3], 0.f)};
-    }
-}
+};
 
 // x / max(||x||, 1e-12) over rows of 512 (one wave per row, in place).
 __global__ __launch_bounds__(256) void nv_rownorm_kernel(float* __restrict__ x, long long rows) {
@@ -358,22 +299,12 @@ int nv_run(const float* wts, const void* image, int layout, int B, int H, int W,
         gtsfm_set_error("netvlad: hipMemsetAsync failed");
         return GTSFM_ERR_HIP;
     }
-    {
-        const int tx = ceil_div(W, NV_C1_T), ty = ceil_div(H, NV_C1_T);
-        hipLaunchKernelGGL(nv_conv1_kernel, dim3((unsigned)B * tx * ty), dim3(256), 0, st, image, layout, H, W, tx, ty, wts + L.w[0], wts + L.b[0],
-                           wts + L.mean, act[0], flag);
-        GTSFM_CHECK_LAUNCH("nv_conv1_kernel");
-    }
+    vgg_launch_conv1(NvLoad{image, layout, wts + L.mean, flag}, B, H, W, wts + L.w[0], wts + L.b[0], act[0], st);
+    GTSFM_CHECK_LAUNCH("vgg_conv1_kernel<NvLoad>");
     if (stage == 0) return hipMemcpyAsync(out, act[0], (size_t)B * H * W * 64 * 4, hipMemcpyDeviceToDevice, st) == hipSuccess ? GTSFM_OK : GTSFM_ERR_HIP;
     int h = H, w = W;
     for (int l = 1; l < NV_LAYERS; ++l) {
-        ConvParams p = {};
-        p.in = act[(l - 1) & 1], p.in_stride = kCin[l], p.in_coff = 0;
-        p.out = act[l & 1], p.out_stride = kCout[l], p.out_coff = 0;
-        p.wpack = wts + L.w[l], p.bias = wts + L.b[l];
-        p.B = B, p.H = h, p.W = w, p.Cin = kCin[l], p.Cout = kCout[l];
-        p.relu = l != NV_LAYERS - 1, p.pool = kPool[l];
-        const int rc = launch_conv3x3(p, st);
+        const int rc = vgg_conv_layer(l, act[(l - 1) & 1], act[l & 1], wts + L.w[l], wts + L.b[l], B, h, w, l != NV_LAYERS - 1, kPool[l], false, st);
         if (rc) return rc;
         if (kPool[l]) h >>= 1, w >>= 1;
     }
@@ -418,12 +349,12 @@ RtWs rt_ws(int n, int d, int with_sim_out) {
     RtWs s;
     const int dp = (d + 31) / 32 * 32;
     const int nstrips = ceil_div(n, RT_STRIP);
-    size_t o = 0;
-    s.pad = o, o += (d % 32 ? align_up((size_t)n * dp * 4, 256) : 0);
-    s.sim = o, o += (with_sim_out ? 0 : align_up((size_t)n * n * 4, 256));
-    s.problems = o, o += align_up((size_t)nstrips * sizeof(GemmProblem), 256);
-    s.counts = o, o += align_up((size_t)nstrips * 2 * 4, 256);
-    s.total = o;
+    WorkspaceCarver c = {};
+    s.pad = c.offset(d % 32 ? (size_t)n * dp * 4 : 0);
+    s.sim = c.offset(with_sim_out ? 0 : (size_t)n * n * 4);
+    s.problems = c.offset((size_t)nstrips * sizeof(GemmProblem));
+    s.counts = c.offset((size_t)nstrips * 2 * 4);
+    s.total = c.used;
     return s;
 }
 
@@ -443,13 +374,7 @@ int gtsfm_netvlad_pack_weights(const float* const* t, int whiten, float* packed)
     const NvLayout L = nv_layout();
     const size_t total = whiten ? L.total_white : L.total_plain;
     for (size_t i = 0; i < L.total_plain; ++i) packed[i] = 0.f;
-    for (int l = 0; l < NV_LAYERS; ++l) {
-        if (l == 0)
-            for (int i = 0; i < 64 * 27; ++i) packed[L.w[0] + i] = t[0][i];
-        else
-            pack_conv3x3_weights(t[2 * l], kCin[l], kCout[l], packed + L.w[l]);
-        for (int o = 0; o < kCout[l]; ++o) packed[L.b[l] + o] = t[2 * l + 1][o];
-    }
+    vgg_pack_convs(t, NV_LAYERS, L.w, L.b, packed);
     for (int i = 0; i < NV_K * NV_D; ++i) packed[L.score + i] = t[26][i];
     for (int i = 0; i < NV_D * NV_K; ++i) packed[L.centers + i] = t[27][i];
     for (int c = 0; c < 3; ++c) packed[L.mean + c] = t[28][c];

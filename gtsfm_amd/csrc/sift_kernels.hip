@@ -121,18 +121,18 @@ struct SiftWs {
 
 SiftWs sift_ws(const SiftGeom& g, int cand_cap, int kp_cap) {
     SiftWs s;
-    size_t o = 0;
-    const size_t full = align_up((size_t)g.H2 * g.W2 * 4, 256);
-    s.pyr = o, o += align_up((size_t)g.floats * 4 + 4, 256);
-    s.tmpA = o, o += full;
-    s.tmpB = o, o += full;
-    s.claim = o, o += align_up((size_t)g.claim_words * 4 + 4, 256);
-    s.cand = o, o += align_up((size_t)cand_cap * 16, 256);
-    s.kps = o, o += align_up((size_t)kp_cap * sizeof(SiftKp), 256);
-    s.ori = o, o += align_up((size_t)kp_cap * sizeof(SiftOri), 256);
-    s.sorted = o, o += align_up((size_t)kp_cap * sizeof(SiftOri), 256);
-    s.counts = o, o += 256;
-    s.total = o;
+    WorkspaceCarver c = {};
+    const size_t full = (size_t)g.H2 * g.W2 * 4;
+    s.pyr = c.offset((size_t)g.floats * 4 + 4);
+    s.tmpA = c.offset(full);
+    s.tmpB = c.offset(full);
+    s.claim = c.offset((size_t)g.claim_words * 4 + 4);
+    s.cand = c.offset((size_t)cand_cap * 16);
+    s.kps = c.offset((size_t)kp_cap * sizeof(SiftKp));
+    s.ori = c.offset((size_t)kp_cap * sizeof(SiftOri));
+    s.sorted = c.offset((size_t)kp_cap * sizeof(SiftOri));
+    s.counts = c.offset(256);
+    s.total = c.used;
     return s;
 }
 

@@ -219,35 +219,30 @@ SpWorkspace sp_workspace_layout(int B, int H, int W) {
     const size_t H2 = H / 2, W2 = W / 2, H4 = H2 / 2, W4 = W2 / 2, Hc = H4 / 2, Wc = W4 / 2;
     const size_t cells = (size_t)B * Hc * Wc, pix8 = cells * 64;
     SpWorkspace ws;
-    size_t o = 0;
-    auto take = [&](size_t bytes) {
-        size_t r = o;
-        o += align_up(bytes, 256);
-        return r;
-    };
+    WorkspaceCarver c = {};
     size_t p0 = (size_t)B * H2 * W2 * 64;  // conv2a out (conv1a's output lives only in LDS, fused into conv1b)
     p0 = p0 > (size_t)B * H4 * W4 * 128 ? p0 : (size_t)B * H4 * W4 * 128;
     p0 = p0 > cells * 512 ? p0 : cells * 512;
     size_t p1 = (size_t)B * H2 * W2 * 64;
     p1 = p1 > cells * 128 ? p1 : cells * 128;
-    ws.ping0 = take(p0 * 4);
-    ws.ping1 = take(p1 * 4);
-    ws.logits = take(cells * 65 * 4);
-    ws.dense = take(cells * 256 * 4);
-    ws.scores = take(pix8 * 4);
-    ws.nms = take(pix8 * 4);
-    ws.ss = take(pix8 * 4);
-    ws.mask = take(pix8);
-    ws.supp = take(pix8);
-    ws.rows = take(((size_t)B * Hc * 8 * 2 + B) * 4);
+    ws.ping0 = c.offset(p0 * 4);
+    ws.ping1 = c.offset(p1 * 4);
+    ws.logits = c.offset(cells * 65 * 4);
+    ws.dense = c.offset(cells * 256 * 4);
+    ws.scores = c.offset(pix8 * 4);
+    ws.nms = c.offset(pix8 * 4);
+    ws.ss = c.offset(pix8 * 4);
+    ws.mask = c.offset(pix8);
+    ws.supp = c.offset(pix8);
+    ws.rows = c.offset(((size_t)B * Hc * 8 * 2 + B) * 4);
     // scratch for the top-k path: one slot per pixel, so that no image can overflow it -- NMS leaves far fewer keypoints
     // on natural images, but a flat or saturated image ties everywhere and keeps every pixel above the threshold; a smaller
     // scratch would drop the bottom rows silently before the top-k. 12 bytes per pixel and image.
     ws.full_capacity = (int)(Hc * 8 * Wc * 8);
-    ws.xy_full = take((size_t)B * ws.full_capacity * 2 * 4);
-    ws.sc_full = take((size_t)B * ws.full_capacity * 4);
-    ws.cnt_full = take((size_t)B * 4);
-    ws.total = o;
+    ws.xy_full = c.offset((size_t)B * ws.full_capacity * 2 * 4);
+    ws.sc_full = c.offset((size_t)B * ws.full_capacity * 4);
+    ws.cnt_full = c.offset((size_t)B * 4);
+    ws.total = c.used;
     return ws;
 }
 
@@ -260,7 +255,9 @@ extern "C" size_t gtsfm_sp_workspace_bytes(int batch, int height, int width) {
 
 extern "C" size_t gtsfm_sp_nms_scratch_bytes(int batch, int h, int w) {
     const size_t n = (size_t)batch * h * w;
-    return align_up(n * 4, 256) + 2 * align_up(n, 256);
+    WorkspaceCarver c = {};
+    c.offset(n * 4), c.offset(n), c.offset(n);  // ss | mask | supp, as gtsfm_sp_simple_nms takes them
+    return c.used;
 }
 
 extern "C" int gtsfm_sp_softmax_d2s(const float* logits_dev, int ld, int batch, int hc, int wc, float* scores_dev, void* stream) {
@@ -272,10 +269,10 @@ extern "C" int gtsfm_sp_simple_nms(const float* scores_dev, int batch, int h, in
                                    void* stream) {
     GTSFM_CHECK_ARG(scores_dev && scratch_dev && out_dev, "sp_simple_nms: null pointer");
     const size_t n = (size_t)batch * h * w;
-    char* s = (char*)scratch_dev;
-    float* ss = (float*)s;
-    uint8_t* mask = (uint8_t*)(s + align_up(n * 4, 256));
-    uint8_t* supp = mask + align_up(n, 256);
+    WorkspaceCarver c = {scratch_dev, 0};
+    float* ss = (float*)c.take(n * 4);
+    uint8_t* mask = (uint8_t*)c.take(n);
+    uint8_t* supp = (uint8_t*)c.take(n);
     return launch_simple_nms(scores_dev, batch, h, w, radius, mask, supp, ss, out_dev, (hipStream_t)stream);
 }
 

@@ -360,19 +360,14 @@ TwLayout tw_layout(int metric, int dim, int row_stride, bool direct, int npairs,
     L.ld = L.direct ? row_stride : tw_words(metric, dim);
     size_t rowParts = 0, colParts = 0;
     for (const TwPair& P : pairs) rowParts += (size_t)P.nChunks * P.nA, colParts += (size_t)P.nRowBlocks * P.nB;
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        const size_t at = off;
-        off = align_up(off + bytes, 256);
-        return at;
-    };
-    L.pairs = take(sizeof(TwPair) * npairs);
-    L.items = take(sizeof(TwItem) * items.size());
-    L.rows = take(L.direct ? 0 : (size_t)rowsTotal * L.ld * 4);
-    L.norms = take((size_t)rowsTotal * 4);
-    L.rowPart = take(rowParts * sizeof(Top2));
-    L.colPart = take(colParts * sizeof(Top2));
-    L.total = off;
+    WorkspaceCarver c = {};
+    L.pairs = c.offset(sizeof(TwPair) * npairs);
+    L.items = c.offset(sizeof(TwItem) * items.size());
+    L.rows = c.offset(L.direct ? 0 : (size_t)rowsTotal * L.ld * 4);
+    L.norms = c.offset((size_t)rowsTotal * 4);
+    L.rowPart = c.offset(rowParts * sizeof(Top2));
+    L.colPart = c.offset(colParts * sizeof(Top2));
+    L.total = c.used;
     return L;
 }
 

@@ -13,6 +13,8 @@ from typing import Dict, List, Sequence, Tuple, Union
 
 import numpy as np
 
+from gtsfm_amd.runtime.engine_base import EngineBase
+
 NUM_CONVS = 10
 # index of each convolution in ``DenseFeatureExtractionModule.model`` (model_test.py:16-39)
 CONV_LAYER_INDEX = (0, 2, 5, 7, 10, 12, 14, 17, 19, 21)
@@ -90,32 +92,19 @@ def pack_weights(weights: Dict[str, object]) -> np.ndarray:
     return out
 
 
-class D2NetEngine:
+class D2NetEngine(EngineBase):
     """Packed weights resident on one device, a cached workspace; one instance per process / GPU."""
 
+    WS_SLACK = "exact"
+
     def __init__(self, weights: Dict[str, object], device=None):
-        import torch
-
-        from gtsfm_amd.runtime import lib as _lib
-        from gtsfm_amd.runtime.superpoint_engine import require_gpu
-
-        self._torch = torch
-        self._L = _lib
-        self._lib = _lib.load()
-        self.device = require_gpu(device)
-        self._weights = torch.from_numpy(pack_weights(weights)).to(self.device)
-        self._ws = None
+        super().__init__(device)
+        self._weights = self._torch.from_numpy(pack_weights(weights)).to(self.device)
         self.relaunches = 0  # forward calls repeated because the candidate list was too small
 
     @classmethod
     def from_checkpoint(cls, path: Union[str, Path], device=None) -> "D2NetEngine":
         return cls(load_checkpoint(path), device)
-
-    def _buffer(self, need: int):
-        if self._ws is None or self._ws.numel() < need:
-            self._ws = None
-            self._ws = self._torch.empty(need, dtype=self._torch.uint8, device=self.device)
-        return self._ws
 
     def _workspace(self, b: int, h: int, w: int, cap: int):
         need = int(self._lib.gtsfm_d2net_workspace_bytes(b, h, w, cap))
@@ -125,7 +114,7 @@ class D2NetEngine:
                 raise RuntimeError(f"D2-Net needs images of at least {MIN_EDGE_PX} x {MIN_EDGE_PX} pixels (got a batch of {b} x {h} x {w})")
             why = self._lib.gtsfm_last_error().decode("utf-8", "replace")
             raise ValueError(f"D2-Net cannot take a batch of {b} x {h} x {w} with {cap} candidate records per image: {why}")
-        return self._buffer(need)
+        return self._grow(need)
 
     def _prepare(self, images: Sequence[np.ndarray]):
         """Equal-sized (H, W, 3) or (H, W) arrays -> (device tensor, layout, B, H, W). uint8 goes to the device as it is; any other dtype is
@@ -247,7 +236,7 @@ class D2NetEngine:
         b, h2, w2 = int(m.shape[0]), int(m.shape[1]), int(m.shape[2])
         cap = int(cand_capacity) if cand_capacity > 0 else 2 * h2 * w2
         k = int(max_keypoints)
-        ws = self._buffer(int(self._lib.gtsfm_d2net_detect_workspace_bytes(b, cap)))
+        ws = self._grow(int(self._lib.gtsfm_d2net_detect_workspace_bytes(b, cap)))
         counts = torch.zeros(b, dtype=torch.int32, device=self.device)
         cand = torch.zeros((b, cap, CANDIDATE_WORDS), dtype=torch.int32, device=self.device)
         kp = torch.empty((b, max(k, 1), 2), dtype=torch.float32, device=self.device)

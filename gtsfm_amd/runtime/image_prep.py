@@ -18,7 +18,7 @@ import numpy as np
 import torch
 
 from gtsfm_amd.runtime import lib as _lib
-from gtsfm_amd.runtime.superpoint_engine import require_gpu
+from gtsfm_amd.runtime.engine_base import EngineBase
 
 
 def downsampled_size(img_h: int, img_w: int, max_resolution: int) -> Tuple[int, int]:
@@ -31,12 +31,11 @@ def downsampled_size(img_h: int, img_w: int, max_resolution: int) -> Tuple[int, 
     return int(np.round(img_h * (max_resolution / float(img_w))).astype(np.int32)), max_resolution
 
 
-class ImagePrep:
-    """Device-resident resize + gray conversion; tap tables are cached per (source size, target size)."""
+class ImagePrep(EngineBase):
+    """Device-resident resize + gray conversion; tap tables are cached per (source size, target size). It needs no workspace."""
 
     def __init__(self, device: Optional[torch.device] = None):
-        self.device = require_gpu(device)
-        self._lib = _lib.load()
+        super().__init__(device)
         self._taps: Dict[Tuple[int, int], Tuple[torch.Tensor, torch.Tensor]] = {}
 
     def _axis_taps(self, dst: int, src: int) -> Tuple[torch.Tensor, torch.Tensor]:

@@ -16,6 +16,8 @@ from typing import Dict, List, Optional, Union
 
 import numpy as np
 
+from gtsfm_amd.runtime.engine_base import EngineBase
+
 HIDDEN, PATCH, FF, TABLE = 768, 14, 3072, 37
 MLP_DIM, CLUSTERS, CLUSTER_DIM, TOKEN_DIM = 512, 64, 256, 256
 SALAD_DIM = TOKEN_DIM + CLUSTERS * CLUSTER_DIM  # 16640
@@ -142,26 +144,19 @@ def position_table(pos_embed: np.ndarray, gh: int, gw: int) -> np.ndarray:
     return np.ascontiguousarray(pos[0].numpy())
 
 
-class MegaLocEngine:
+class MegaLocEngine(EngineBase):
     """Packed weights resident on one device, position tables cached per grid, a cached workspace; one instance per process / GPU."""
 
+    WS_SLACK = "exact"
+
     def __init__(self, weights: Dict[str, object], device=None):
-        import torch
-
-        from gtsfm_amd.runtime import lib as _lib
-        from gtsfm_amd.runtime.superpoint_engine import require_gpu
-
-        self._torch = torch
-        self._L = _lib
-        self._lib = _lib.load()
-        self.device = require_gpu(device)
+        super().__init__(device)
         w = normalise_weights(weights)
         self.depth, self.feat_dim = depth_of(w), int(w[AGG + "linear.bias"].size)
         self._pos_embed = w[BB + "pos_embed"]
-        self._weights = torch.from_numpy(pack_weights(w)).to(self.device)
+        self._weights = self._torch.from_numpy(pack_weights(w)).to(self.device)
         self._pos: Dict[tuple, object] = {}
-        self._ws: Optional[object] = None
-        self._flag = torch.zeros(1, dtype=torch.int32, device=self.device)
+        self._flag = self._torch.zeros(1, dtype=self._torch.int32, device=self.device)
 
     @classmethod
     def from_checkpoint(cls, path: Union[str, Path], device=None) -> "MegaLocEngine":
@@ -176,10 +171,7 @@ class MegaLocEngine:
         need = int(self._lib.gtsfm_megaloc_workspace_bytes(b, h, w, self.feat_dim))
         if need == 0:
             raise ValueError(f"MegaLoc needs height and width that are multiples of {PATCH} and more than {CLUSTERS} patches (got a batch of {b} x {h} x {w})")
-        if self._ws is None or self._ws.numel() < need:
-            self._ws = None
-            self._ws = self._torch.empty(need, dtype=self._torch.uint8, device=self.device)
-        return self._ws
+        return self._grow(need)
 
     def _prepare(self, images):
         """(B, 3, H, W), normalised float (any float dtype: converted to float32) or raw uint8, CPU or device -> (device tensor, layout, B, H, W).

@@ -13,6 +13,8 @@ from typing import Dict, List, Optional, Union
 
 import numpy as np
 
+from gtsfm_amd.runtime.engine_base import EngineBase
+
 NUM_CONVS = 13
 # index of each VGG16 convolution among the backbone's 29 children (conv / ReLU / max-pool), = its index in ``net.layers``
 CONV_LAYER_INDEX = (0, 2, 5, 7, 10, 12, 14, 17, 19, 21, 24, 26, 28)
@@ -75,23 +77,16 @@ def pack_weights(weights: Dict[str, object], whiten: bool = True) -> np.ndarray:
     return out
 
 
-class NetVLADEngine:
+class NetVLADEngine(EngineBase):
     """Packed weights resident on one device, a cached workspace; one instance per process / GPU."""
 
+    WS_SLACK = "exact"
+
     def __init__(self, weights: Dict[str, object], device=None, whiten: bool = True):
-        import torch
-
-        from gtsfm_amd.runtime import lib as _lib
-        from gtsfm_amd.runtime.superpoint_engine import require_gpu
-
-        self._torch = torch
-        self._L = _lib
-        self._lib = _lib.load()
-        self.device = require_gpu(device)
+        super().__init__(device)
         self.whiten = bool(whiten)
-        self._weights = torch.from_numpy(pack_weights(weights, whiten)).to(self.device)
-        self._ws: Optional[object] = None
-        self._flag = torch.zeros(1, dtype=torch.int32, device=self.device)
+        self._weights = self._torch.from_numpy(pack_weights(weights, whiten)).to(self.device)
+        self._flag = self._torch.zeros(1, dtype=self._torch.int32, device=self.device)
 
     @classmethod
     def from_checkpoint(cls, path: Union[str, Path], device=None, whiten: bool = True) -> "NetVLADEngine":
@@ -102,10 +97,7 @@ class NetVLADEngine:
         if need == 0:
             # the reference raises RuntimeError too (torch's max_pool2d: the fourth pool's output would be empty)
             raise RuntimeError(f"NetVLAD needs images of at least 16 x 16 pixels (got a batch of {b} x {h} x {w})")
-        if self._ws is None or self._ws.numel() < need:
-            self._ws = None
-            self._ws = self._torch.empty(need, dtype=self._torch.uint8, device=self.device)
-        return self._ws
+        return self._grow(need)
 
     def _prepare(self, images):
         """(B, 3, H, W) float (any float dtype: converted to float32) or (B, H, W, 3) uint8, CPU or device -> (device tensor, layout, B, H, W).

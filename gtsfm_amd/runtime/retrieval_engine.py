@@ -8,6 +8,8 @@ from typing import List, Optional, Tuple
 
 import numpy as np
 
+from gtsfm_amd.runtime.engine_base import EngineBase
+
 
 def pairs_from_topk(idx: np.ndarray) -> List[Tuple[int, int]]:
     """[N][k] column indices (-1 = empty rank) -> (i, j) pairs, row-major over (i, rank): the order of the reference's
@@ -16,20 +18,10 @@ def pairs_from_topk(idx: np.ndarray) -> List[Tuple[int, int]]:
     return [(int(i), int(idx[i, r])) for i, r in zip(rows, ranks)]
 
 
-class RetrievalEngine:
+class RetrievalEngine(EngineBase):
     """Lib handle and a cached workspace; one instance per process / GPU."""
 
-    def __init__(self, device=None):
-        import torch
-
-        from gtsfm_amd.runtime import lib as _lib
-        from gtsfm_amd.runtime.superpoint_engine import require_gpu
-
-        self._torch = torch
-        self._L = _lib
-        self._lib = _lib.load()
-        self.device = require_gpu(device)
-        self._ws = None
+    WS_SLACK = "exact"
 
     def topk(self, descriptors, k: int, min_score: Optional[float], blocksize: int = 50, with_sim: bool = False):
         """``descriptors``: (N, D) float32, host array or tensor (CPU or device). Returns device tensors idx [N][min(k, N)] int32,
@@ -44,15 +36,13 @@ class RetrievalEngine:
         need = int(self._lib.gtsfm_retrieval_workspace_bytes(n, dim, int(with_sim)))
         if need == 0:
             raise ValueError(f"retrieval needs at least one descriptor of dimension >= 1 (got shape {(n, dim)})")
-        if self._ws is None or self._ws.numel() < need:
-            self._ws = None
-            self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        ws = self._grow(need)
         idx = torch.empty((n, kk), dtype=torch.int32, device=self.device)
         scores = torch.empty((n, kk), dtype=torch.float32, device=self.device)
         sim = torch.empty((n, n), dtype=torch.float32, device=self.device) if with_sim else None
         threshold = float("-inf") if min_score is None else float(min_score)
         rc = self._lib.gtsfm_retrieval_topk(d.data_ptr(), n, dim, int(k), threshold, int(blocksize), idx.data_ptr(), scores.data_ptr(),
-                                            None if sim is None else sim.data_ptr(), self._ws.data_ptr(), self._ws.numel(),
+                                            None if sim is None else sim.data_ptr(), ws.data_ptr(), ws.numel(),
                                             self._L.current_stream_handle())
         self._L.check(rc, "gtsfm_retrieval_topk")
         return idx, scores, sim

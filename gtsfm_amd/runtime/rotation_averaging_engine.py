@@ -8,6 +8,8 @@ from typing import Dict, Optional
 
 import numpy as np
 
+from gtsfm_amd.runtime.engine_base import EngineBase
+
 COUNTER_FIELDS = ("status", "outer_iterations", "accepted_steps", "hessian_applications", "chordal_cg_steps", "component_size", "anchor", "valid_rows")
 COST_FIELDS = ("initial_cost", "chordal_cost", "final_cost", "gradient_inf_norm")
 STATUS_NAMES = ("CONVERGED", "MAX_ITERATIONS", "NO_VALID_ROW", "NON_FINITE")
@@ -16,28 +18,12 @@ CONVERGED, MAX_ITERATIONS, NO_VALID_ROW, NON_FINITE = 0, 1, 2, 3
 DEFAULTS = dict(chordal_tol=1e-10, chordal_max_iterations=2000, delta0=1.0, kappa_cg=0.1, theta=1.0, gradient_tol=1e-9, max_outer=100, max_inner=0)
 
 
-class RotationAveragingEngine:
-    """Lib handle and a cached workspace; one instance per process / GPU."""
-
-    def __init__(self, device=None):
-        import torch
-
-        from gtsfm_amd.runtime import lib as _lib
-        from gtsfm_amd.runtime.superpoint_engine import require_gpu
-
-        self._torch = torch
-        self.device = require_gpu(device)
-        self._L = _lib
-        self._lib = _lib.load()
-        self._ws = None
-
+class RotationAveragingEngine(EngineBase):
     def _workspace(self, *sizes):
         need = int(self._lib.gtsfm_rotation_averaging_workspace_bytes(*sizes))
         if need == 0:
             raise ValueError(f"gtsfm_rotation_averaging_workspace_bytes refuses {sizes}")
-        if self._ws is None or self._ws.numel() < need:
-            self._ws = self._torch.empty(need + 256, dtype=self._torch.uint8, device=self.device)
-        return self._ws
+        return self._grow(need)
 
     def average(self, pair_images, rotation, weight, pair_enable=None, *, num_images: int, anchor: int = -1, problem_row_off=None, **options) -> Dict[str, object]:
         """Device tensors as in include/gtsfm_amd.h: ``pair_images`` [E, 2] int32 = (i1, i2), ``rotation`` [E, 9] float64 = i2Ri1, ``weight`` [E]

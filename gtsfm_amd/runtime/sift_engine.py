@@ -11,6 +11,8 @@ from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 
+from gtsfm_amd.runtime.engine_base import EngineBase
+
 DESCRIPTOR_DIM = 128
 CANDIDATE_WORDS = 4  # int32 octave, layer, row, column
 KEYPOINT_WORDS = 8  # the four above, then float32 x, y (octave coordinates), scl, response
@@ -44,20 +46,13 @@ def split_keypoints(records: np.ndarray) -> Dict[str, np.ndarray]:
     return out
 
 
-class SiftEngine:
+class SiftEngine(EngineBase):
     """A cached workspace on one device; one instance per process / GPU."""
 
+    WS_SLACK = "exact"
+
     def __init__(self, device=None):
-        import torch
-
-        from gtsfm_amd.runtime import lib as _lib
-        from gtsfm_amd.runtime.superpoint_engine import require_gpu
-
-        self._torch = torch
-        self._L = _lib
-        self._lib = _lib.load()
-        self.device = require_gpu(device)
-        self._ws = None
+        super().__init__(device)
         self.relaunches = 0  # calls repeated because a candidate or keypoint list was too small
 
     def _workspace(self, b: int, h: int, w: int, cand: int, kp: int):
@@ -65,10 +60,7 @@ class SiftEngine:
         if need == 0:
             why = self._lib.gtsfm_last_error().decode("utf-8", "replace")
             raise ValueError(f"SIFT cannot take a batch of {b} x {h} x {w} with capacities {cand} / {kp}: {why}")
-        if self._ws is None or self._ws.numel() < need:
-            self._ws = None
-            self._ws = self._torch.empty(need, dtype=self._torch.uint8, device=self.device)
-        return self._ws
+        return self._grow(need)
 
     def _gray(self, images: Sequence[np.ndarray]):
         """Equal-sized uint8 images -> [B][H][W] uint8 on the device; colour goes through ``gtsfm_prep_rgb_to_gray_u8``."""

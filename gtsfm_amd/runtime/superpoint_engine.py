@@ -18,6 +18,7 @@ import numpy as np
 import torch
 
 from gtsfm_amd.runtime import lib as _lib
+from gtsfm_amd.runtime.engine_base import require_gpu  # noqa: F401  (imported from here by older callers)
 
 # checkpoint order of superpoint_v1.pth (superpoint.py:119-134)
 SUPERPOINT_KEYS = [
@@ -32,12 +33,6 @@ SUPERPOINT_KEYS = [
 DEFAULT_NMS_RADIUS = 4  # superpoint.py:111-115 default_config
 DEFAULT_KEYPOINT_THRESHOLD = 0.005
 DEFAULT_REMOVE_BORDERS = 4
-
-
-def require_gpu(device: Optional[torch.device] = None) -> torch.device:
-    if not torch.cuda.is_available():
-        raise RuntimeError("gtsfm_amd requires an AMD GPU visible to PyTorch-ROCm; there is no CPU fallback.")
-    return torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
 
 
 def pack_superpoint_weights(state_dict: Mapping[str, torch.Tensor]) -> np.ndarray:

@@ -8,37 +8,17 @@ from typing import Dict, Iterable, List, Optional, Sequence, Tuple
 
 import numpy as np
 
+from gtsfm_amd.runtime.engine_base import EngineBase
+
 COUNT_FIELDS = ("tracks", "measurements", "discarded", "components", "rounds")
 
 
-class TracksEngine:
-    """Lib handle and a cached workspace; one instance per process / GPU."""
-
-    def __init__(self, device=None):
-        import torch
-
-        from gtsfm_amd.runtime import lib as _lib
-        from gtsfm_amd.runtime.superpoint_engine import require_gpu
-
-        self._torch = torch
-        self.device = require_gpu(device)
-        self._L = _lib
-        self._lib = _lib.load()
-        self._ws = None
-
+class TracksEngine(EngineBase):
     def _workspace(self, num_nodes: int, total: int):
         need = int(self._lib.gtsfm_tracks_workspace_bytes(num_nodes, total))
         if need == 0 and num_nodes > 0:
             raise ValueError(f"gtsfm_tracks_workspace_bytes refuses {num_nodes} nodes / {total} match rows")
-        if self._ws is None or self._ws.numel() < need:
-            self._ws = self._torch.empty(need + 256, dtype=self._torch.uint8, device=self.device)
-        return self._ws
-
-    def _dev(self, a, dtype):
-        torch = self._torch
-        if isinstance(a, torch.Tensor):
-            return a.to(device=self.device, dtype=dtype).contiguous()
-        return torch.from_numpy(np.ascontiguousarray(a, dtype={torch.int32: np.int32, torch.int64: np.int64, torch.uint8: np.uint8}[dtype])).to(self.device)
+        return self._grow(need)
 
     def tracks_from_device(self, match_idx, match_off, pair_images, node_off, match_count=None, mask=None, pair_enable=None, kp_xy=None,
                            num_nodes: Optional[int] = None) -> Dict[str, object]:

@@ -9,6 +9,8 @@ from typing import Dict, Optional
 
 import numpy as np
 
+from gtsfm_amd.runtime.engine_base import EngineBase
+
 COUNT_FIELDS = ("pair_edges", "measurement_edges", "nodes", "inlier_pairs", "inlier_measurements", "inlier_cameras")
 OUTLIER_WEIGHT_THRESHOLD = 0.125
 LDS_NODES = 2048  # TR_LDS_NODES of translation_kernels.hip
@@ -22,28 +24,12 @@ def lds_node_limit(value: Optional[int] = None) -> int:
     return LDS_NODES if value < 0 or value > LDS_NODES else int(value)
 
 
-class TranslationInliersEngine:
-    """Lib handle and a cached workspace; one instance per process / GPU."""
-
-    def __init__(self, device=None):
-        import torch
-
-        from gtsfm_amd.runtime import lib as _lib
-        from gtsfm_amd.runtime.superpoint_engine import require_gpu
-
-        self._torch = torch
-        self.device = require_gpu(device)
-        self._L = _lib
-        self._lib = _lib.load()
-        self._ws = None
-
+class TranslationInliersEngine(EngineBase):
     def _workspace(self, *sizes):
         need = int(self._lib.gtsfm_translation_inliers_workspace_bytes(*sizes))
         if need == 0:
             raise ValueError(f"gtsfm_translation_inliers_workspace_bytes refuses {sizes}")
-        if self._ws is None or self._ws.numel() < need:
-            self._ws = self._torch.empty(need + 256, dtype=self._torch.uint8, device=self.device)
-        return self._ws
+        return self._grow(need)
 
     def inliers(self, pair_images, pair_direction, pair_enable, rotation, rotation_valid, intrinsics, track_off, image, uv, track_enable, meas_enable, directions, *,
                 threshold: float = OUTLIER_WEIGHT_THRESHOLD, world=None, node_capacity: Optional[int] = None, lds_nodes: Optional[int] = None,

@@ -8,6 +8,8 @@ from typing import Dict, Optional
 
 import numpy as np
 
+from gtsfm_amd.runtime.engine_base import EngineBase
+
 MODES = ("NO_RANSAC", "RANSAC_SAMPLE_UNIFORM", "RANSAC_SAMPLE_BIASED_BASELINE", "RANSAC_TOPK_BASELINES")
 MAX_HYPOTHESES = (1 << 31) - 1  # a track has fewer pairs than this (at most 65535 measurements)
 CAMERA_FIELDS = 17  # valid, fx, fy, cx, cy, wRc row-major, wtc
@@ -39,34 +41,12 @@ def pack_cameras(cameras: Dict[int, object], num_images: Optional[int] = None) -
     return table
 
 
-class TriangulationEngine:
-    """Lib handle and a cached workspace; one instance per process / GPU."""
-
-    def __init__(self, device=None):
-        import torch
-
-        from gtsfm_amd.runtime import lib as _lib
-        from gtsfm_amd.runtime.superpoint_engine import require_gpu
-
-        self._torch = torch
-        self.device = require_gpu(device)
-        self._L = _lib
-        self._lib = _lib.load()
-        self._ws = None
-
+class TriangulationEngine(EngineBase):
     def _workspace(self, num_tracks: int, total: int, max_hyp: int):
         need = int(self._lib.gtsfm_triangulate_workspace_bytes(num_tracks, total, max_hyp))
         if need == 0:
             raise ValueError(f"gtsfm_triangulate_workspace_bytes refuses {num_tracks} tracks / {total} measurements / {max_hyp} hypotheses")
-        if self._ws is None or self._ws.numel() < need:
-            self._ws = self._torch.empty(need + 256, dtype=self._torch.uint8, device=self.device)
-        return self._ws
-
-    def _dev(self, a, dtype, np_dtype):
-        torch = self._torch
-        if isinstance(a, torch.Tensor):
-            return a.to(device=self.device, dtype=dtype).contiguous()
-        return torch.from_numpy(np.ascontiguousarray(a, dtype=np_dtype)).to(self.device)
+        return self._grow(need)
 
     def triangulate(self, track_off, image, uv, cameras, mode="NO_RANSAC", reproj_error_threshold: float = float("inf"),
                     min_triangulation_angle_deg: float = 0.0, num_hypotheses: int = 2749, seed: int = 0) -> Dict[str, object]:
@@ -75,10 +55,10 @@ class TriangulationEngine:
         ``exit_code`` [T] int32, ``inlier_mask`` [S] uint8, ``stats`` [T, 4] int32."""
         torch = self._torch
         mode_id = MODES.index(getattr(mode, "name", mode)) if not isinstance(mode, int) else int(mode)
-        off = self._dev(track_off, torch.int64, np.int64)
-        img = self._dev(image, torch.int32, np.int32)
-        xy = self._dev(uv, torch.float32, np.float32).reshape(-1, 2)
-        cams = self._dev(cameras, torch.float64, np.float64).reshape(-1, CAMERA_FIELDS)
+        off = self._dev(track_off, torch.int64)
+        img = self._dev(image, torch.int32)
+        xy = self._dev(uv, torch.float32).reshape(-1, 2)
+        cams = self._dev(cameras, torch.float64).reshape(-1, CAMERA_FIELDS)
         num_tracks, total = int(off.numel()) - 1, int(img.numel())
         if num_tracks < 0 or int(xy.shape[0]) != total:
             raise ValueError(f"track_off has {off.numel()} entries; image has {total} and uv {xy.shape[0]} measurements")

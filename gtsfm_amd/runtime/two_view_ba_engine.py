@@ -9,7 +9,7 @@ import dataclasses
 import math
 from typing import Dict, Optional
 
-import numpy as np
+from gtsfm_amd.runtime.engine_base import EngineBase
 
 STATUS_NAMES = ("OK", "SKIPPED", "NO_INITIAL_POSE", "NONE_TRIANGULATED", "INDETERMINATE")
 STATS_FIELDS = ("status", "verified", "triangulated", "valid", "accepted_steps", "solves_tried", "spare0", "spare1")
@@ -31,34 +31,12 @@ class TwoViewBAOptions:
     triangulation_min_angle_deg: float = 0.0
 
 
-class TwoViewBAEngine:
-    """Lib handle and a cached workspace; one instance per process / GPU."""
-
-    def __init__(self, device=None):
-        import torch
-
-        from gtsfm_amd.runtime import lib as _lib
-        from gtsfm_amd.runtime.superpoint_engine import require_gpu
-
-        self._torch = torch
-        self.device = require_gpu(device)
-        self._L = _lib
-        self._lib = _lib.load()
-        self._ws = None
-
+class TwoViewBAEngine(EngineBase):
     def _workspace(self, num_pairs: int, total: int):
         need = int(self._lib.gtsfm_two_view_ba_workspace_bytes(num_pairs, total))
         if need == 0:
             raise ValueError(f"gtsfm_two_view_ba_workspace_bytes refuses {num_pairs} pairs / {total} matches")
-        if self._ws is None or self._ws.numel() < need:
-            self._ws = self._torch.empty(need + 256, dtype=self._torch.uint8, device=self.device)
-        return self._ws
-
-    def _dev(self, a, dtype, np_dtype):
-        torch = self._torch
-        if isinstance(a, torch.Tensor):
-            return a.to(device=self.device, dtype=dtype).contiguous()
-        return torch.from_numpy(np.ascontiguousarray(a, dtype=np_dtype)).to(self.device)
+        return self._grow(need)
 
     def run(self, launch: Dict[str, object], options: Optional[TwoViewBAOptions] = None) -> Dict[str, object]:
         """``launch``: one verifier launch's arrays, device tensors (used where they lie) or host arrays -- ``kp_xy`` [*, 2] float32,
@@ -69,16 +47,16 @@ class TwoViewBAEngine:
         0 .. M raises)."""
         torch = self._torch
         opt = options or TwoViewBAOptions()
-        kp = self._dev(launch["kp_xy"], torch.float32, np.float32).reshape(-1, 2)
-        off1 = self._dev(launch["kp_off1"], torch.int64, np.int64)
-        off2 = self._dev(launch["kp_off2"], torch.int64, np.int64)
-        idx = self._dev(launch["match_idx"], torch.int32, np.int32).reshape(-1, 2)
-        moff = self._dev(launch["match_off"], torch.int64, np.int64)
-        count = None if launch.get("match_count") is None else self._dev(launch["match_count"], torch.int32, np.int32)
-        mask = self._dev(launch["inlier_mask"], torch.uint8, np.uint8)
-        intr = self._dev(launch["intrinsics"], torch.float64, np.float64).reshape(-1, 8)
-        rot = self._dev(launch["rotation"], torch.float64, np.float64).reshape(-1, 9)
-        trans = self._dev(launch["translation"], torch.float64, np.float64).reshape(-1, 3)
+        kp = self._dev(launch["kp_xy"], torch.float32).reshape(-1, 2)
+        off1 = self._dev(launch["kp_off1"], torch.int64)
+        off2 = self._dev(launch["kp_off2"], torch.int64)
+        idx = self._dev(launch["match_idx"], torch.int32).reshape(-1, 2)
+        moff = self._dev(launch["match_off"], torch.int64)
+        count = None if launch.get("match_count") is None else self._dev(launch["match_count"], torch.int32)
+        mask = self._dev(launch["inlier_mask"], torch.uint8)
+        intr = self._dev(launch["intrinsics"], torch.float64).reshape(-1, 8)
+        rot = self._dev(launch["rotation"], torch.float64).reshape(-1, 9)
+        trans = self._dev(launch["translation"], torch.float64).reshape(-1, 3)
         num_pairs, total = int(off1.numel()), int(idx.shape[0])
         if not (off2.numel() == num_pairs and moff.numel() == num_pairs + 1 and intr.shape[0] == num_pairs and rot.shape[0] == num_pairs
                 and trans.shape[0] == num_pairs and mask.numel() == total and (count is None or count.numel() == num_pairs)):

@@ -12,6 +12,8 @@ from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 
+from gtsfm_amd.runtime.engine_base import EngineBase
+
 HAMMING = 1
 EUCLIDEAN = 2
 
@@ -50,20 +52,8 @@ def kept_in_distance_order(matches0: np.ndarray, dist0: np.ndarray) -> np.ndarra
     return np.stack([rows, matches0[rows]], axis=1).astype(np.uint32)
 
 
-class TwoWayEngine:
-    """Lib handle and a cached workspace; one instance per process / GPU."""
-
-    def __init__(self, device=None):
-        import torch
-
-        from gtsfm_amd.runtime import lib as _lib
-        from gtsfm_amd.runtime.superpoint_engine import require_gpu
-
-        self._torch = torch
-        self.device = require_gpu(device)
-        self._L = _lib
-        self._lib = _lib.load()
-        self._ws = None
+class TwoWayEngine(EngineBase):
+    WS_SLACK = "quarter"
 
     def match_raw(self, table, dim: int, pairs: Sequence[Tuple[int, int, int, int]], metric: int = EUCLIDEAN, ratio: Optional[float] = None):
         """Device call. ``table``: 2-D device tensor (float32 or uint8), row r = descriptor r (first ``dim`` entries);
@@ -77,14 +67,13 @@ class TwoWayEngine:
         need = int(self._lib.gtsfm_twoway_workspace_bytes(is_u8, metric, dim, table.stride(0), len(p4), p4.ctypes.data))
         if need == 0:
             self._L.check(-1, "gtsfm_twoway_workspace_bytes")
-        if self._ws is None or self._ws.numel() < need:
-            self._ws = torch.empty(int(need * 1.25) + 256, dtype=torch.uint8, device=self.device)
+        ws = self._grow(need)
         total = int(p4[:, 1].sum())
         matches0 = torch.empty(total, dtype=torch.int32, device=self.device)
         dist0 = torch.empty(total, dtype=torch.float32, device=self.device)
         rc = self._lib.gtsfm_twoway_match(
             table.data_ptr(), is_u8, metric, dim, table.stride(0), len(p4), p4.ctypes.data, int(ratio is not None),
-            float(ratio) if ratio is not None else 0.0, self._ws.data_ptr(), self._ws.numel(), matches0.data_ptr(), dist0.data_ptr(),
+            float(ratio) if ratio is not None else 0.0, ws.data_ptr(), ws.numel(), matches0.data_ptr(), dist0.data_ptr(),
             self._L.current_stream_handle(),
         )
         self._L.check(rc, "gtsfm_twoway_match")

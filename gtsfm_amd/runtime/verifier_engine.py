@@ -12,30 +12,18 @@ import numpy as np
 import torch
 
 from gtsfm_amd.runtime import lib as _lib
-from gtsfm_amd.runtime.superpoint_engine import require_gpu
+from gtsfm_amd.runtime.engine_base import EngineBase
 
-_NUMPY_DTYPE = {torch.int32: np.int32, torch.int64: np.int64, torch.float64: np.float64}
 STATS_FIELDS = ("inliers", "hypotheses", "winner_hypothesis", "winner_root", "good_r1_t", "good_r2_t", "good_r1_mt", "good_r2_mt")
 
 
-class VerifierEngine:
+class VerifierEngine(EngineBase):
     """Stateless apart from a cached workspace; one instance per process / GPU."""
 
-    def __init__(self, device: Optional[torch.device] = None):
-        self.device = require_gpu(device)
-        self._lib = _lib.load()
-        self._ws: Optional[torch.Tensor] = None
+    WS_SLACK = "quarter"
 
     def _workspace(self, total_matches: int) -> torch.Tensor:
-        need = int(self._lib.gtsfm_verify_workspace_bytes(total_matches))
-        if self._ws is None or self._ws.numel() < need:
-            self._ws = torch.empty(int(need * 1.25) + 256, dtype=torch.uint8, device=self.device)
-        return self._ws
-
-    def _dev(self, a, dtype) -> torch.Tensor:
-        if isinstance(a, torch.Tensor):
-            return a.to(device=self.device, dtype=dtype).contiguous()
-        return torch.from_numpy(np.ascontiguousarray(a, dtype=_NUMPY_DTYPE[dtype])).to(self.device)
+        return self._grow(int(self._lib.gtsfm_verify_workspace_bytes(total_matches)))
 
     def verify_batch(
         self,

@@ -10,6 +10,8 @@ from typing import Dict
 
 import numpy as np
 
+from gtsfm_amd.runtime.engine_base import EngineBase
+
 MIN_EDGE_ERROR, MEDIAN_EDGE_ERROR = 0, 1
 CRITERIA = {"MIN_EDGE_ERROR": MIN_EDGE_ERROR, "MEDIAN_EDGE_ERROR": MEDIAN_EDGE_ERROR}
 FILTER_COUNT_FIELDS = ("input_edges", "kept_edges", "triplets", "max_triplets_per_edge")
@@ -29,29 +31,16 @@ def criterion_code(criterion) -> int:
     return int(criterion)
 
 
-class ViewGraphEngine:
-    """Lib handle and a cached workspace; one instance per process / GPU."""
-
+class ViewGraphEngine(EngineBase):
     def __init__(self, device=None):
-        import torch
-
-        from gtsfm_amd.runtime import lib as _lib
-        from gtsfm_amd.runtime.superpoint_engine import require_gpu
-
-        self._torch = torch
-        self.device = require_gpu(device)
-        self._L = _lib
-        self._lib = _lib.load()
-        self._ws = None
+        super().__init__(device)
         self._triplet_capacity = 0
 
     def _workspace(self, num_edges: int, num_images: int, triplets: int):
         need = int(self._lib.gtsfm_view_graph_workspace_bytes(num_edges, num_images, triplets))
         if need == 0:
             raise ValueError(f"gtsfm_view_graph_workspace_bytes refuses {num_edges} edges / {num_images} images / {triplets} triplets")
-        if self._ws is None or self._ws.numel() < need:
-            self._ws = self._torch.empty(need + 256, dtype=self._torch.uint8, device=self.device)
-        return self._ws
+        return self._grow(need)
 
     def _check(self, pair_images, rotation, pair_enable, num_images):
         torch = self._torch
