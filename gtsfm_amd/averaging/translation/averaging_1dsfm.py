@@ -6,10 +6,15 @@ from numpy's global generator exactly as the reference calls it, the track selec
 Directions are 3-vectors or anything with ``.point3()``; rotations are 3 x 3 arrays or anything with ``.matrix()``; calibrations are of the
 pure pinhole family of ``gtsfm_amd.common.calibration.pinhole_parameters`` (anything else raises ``NotImplementedError``).
 
-Out of scope: ``TranslationRecovery`` (gtsam's Levenberg-Marquardt over chordal factors; ``run_translation_averaging`` hands the inliers to a
-``translation_recovery`` callable, by default a thin wrapper that needs gtsam and is not tested here), Shonan rotation averaging,
-``rig_1dsfm.py``, the Dask graph and the ground-truth metrics. PARITY UNPINNED: gtsam's MFAS picks among several roots or tied scores in the
-order of an ``unordered_map`` (here: the smallest node id); ``Unit3``'s normalisation in the last bits; distortion models."""
+``run_translation_averaging`` hands the inliers to a ``translation_recovery`` callable. The default is a thin wrapper around gtsam's
+``TranslationRecovery`` (it needs gtsam and is not tested here); ``translation_recovery="device"`` selects ``device_translation_recovery``,
+which solves the same robust chordal problem on the device (``gtsfm_translation_recovery_f64``, gtsfm_amd/csrc/translation_recovery_kernels.hip;
+``recover_arrays`` is the same over arrays). Out of scope: relative and absolute pose priors, ``rig_1dsfm.py``, the Dask graph and the
+ground-truth metrics. PARITY UNPINNED: gtsam's MFAS picks among several roots or tied scores in the order of an ``unordered_map`` (here: the
+smallest node id); ``Unit3``'s normalisation in the last bits; distortion models; of the recovery, gtsam's Levenberg-Marquardt path and its
+seeded random start (here a deterministic linear start), its soft prior on the first key (here a hard anchor), ``Unit3`` and the
+2-dimensional noise model of the reference's gtsam version (here the 3-vector chordal residual with the same sigma). No local-minimum
+guarantee is claimed."""
 
 from __future__ import annotations
 
@@ -173,6 +178,57 @@ def default_translation_recovery(num_images, w_i2Ui1_dict, w_iUj_dict_tracks, wR
     return [values.atPoint3(C(i)) if wRi_list[i] is not None and values.exists(C(i)) else None for i in range(num_images)]
 
 
+_recovery_engines: Dict[str, Any] = {}
+
+
+def recovery_engine(device=None):
+    """The process's ``TranslationRecoveryEngine`` for ``device`` (None: the current one)."""
+    key = str(device)
+    if key not in _recovery_engines:
+        from gtsfm_amd.runtime.translation_recovery_engine import TranslationRecoveryEngine
+
+        _recovery_engines[key] = TranslationRecoveryEngine(device)
+    return _recovery_engines[key]
+
+
+def device_translation_recovery(num_images, w_i2Ui1_dict, w_iUj_dict_tracks, wRi_list, i2Ti1_priors, absolute_pose_priors, scale_factor, robust_measurement_noise,  # noqa: N803
+                                device=None, **options):
+    """``TranslationRecovery`` on the device, with the signature of ``default_translation_recovery``: the inlier measurements as dicts in, a
+    list of ``wti`` (or None for a camera without a rotation or outside the first measurement's component, as the reference's
+    ``values.exists`` check gives) out. sigma and Huber's k are the reference's; ``options``: further keys of the engine's ``DEFAULTS``."""
+    if len(i2Ti1_priors) > 0:
+        raise NotImplementedError("relative pose priors are not handled by device_translation_recovery")
+    _, _, pairs, world_pair, track_off, image, world_meas = TranslationAveraging1DSFM._dicts_to_arrays(w_i2Ui1_dict, w_iUj_dict_tracks)
+    if len(pairs) + len(image) == 0:
+        return [None] * num_images
+    eng = recovery_engine(device)
+    dev = eng.upload(pairs, world_pair, None, track_off, image, world_meas, None)
+    out = eng.recover(*dev, num_images=num_images, scale_factor=scale_factor, sigma=NOISE_MODEL_SIGMA, huber_k=HUBER_LOSS_K if robust_measurement_noise else 0.0, **options)
+    wti, valid = out["translation"][0].cpu().numpy(), out["node_valid"][0].cpu().numpy()
+    return [wti[i].copy() if wRi_list[i] is not None and valid[i] else None for i in range(num_images)]
+
+
+class TranslationAverages:
+    """What ``VerifiedScene.translation_averaging`` returns: ``wti_list`` (a position or None per image), ``wTi_list`` ((wRi, wti) or None),
+    ``landmarks`` [T, 3] (NaN for a track that took no part), ``inliers`` (the ``TranslationInliers`` of the rejection, whose ``.edges``
+    feeds ``tracks()``), ``status``, ``counters``, ``costs``. ``read_back()`` downloads the rows the recovery ran on."""
+
+    def __init__(self, wRi_list, wti_list, landmarks, inliers, status, counters, costs, device_rows=None) -> None:  # noqa: N803
+        self.wRi_list, self.wti_list, self.landmarks, self.inliers = wRi_list, wti_list, landmarks, inliers
+        self.status, self.counters, self.costs, self._device_rows = status, counters, costs, device_rows
+        self.wTi_list = [(matrix3(r), t) if r is not None and t is not None else None for r, t in zip(wRi_list, wti_list)]
+
+    def cameras(self, intrinsics) -> Dict[int, Any]:
+        """{image: PinholeCamera} of the images with a pose and a calibration: the ``cameras`` argument of ``triangulate``."""
+        from gtsfm_amd.common.calibration import PinholeCamera
+
+        return {i: PinholeCamera(p[0], p[1], intrinsics[i]) for i, p in enumerate(self.wTi_list) if p is not None and i < len(intrinsics) and intrinsics[i] is not None}
+
+    def read_back(self) -> Dict[str, np.ndarray]:
+        """Host copies of the recovery's inputs: ``pair_images``, ``world_pair``, ``pair_enable``, ``track_off``, ``image``, ``world_meas``, ``meas_enable``."""
+        return {k: (None if v is None else v.cpu().numpy()) for k, v in (self._device_rows or {}).items()}
+
+
 class TranslationInliers:
     """What ``compute_inliers_arrays`` and ``VerifiedScene.translation_inliers`` return: ``pairs`` the pair rows, ``pair_weight`` their mean
     outlier weights (NaN for a row that did not take part), ``pair_inlier`` the mask; ``edges`` the inlier pairs in row order (the ``edges=``
@@ -215,7 +271,10 @@ class TranslationAveraging1DSFM(GTSFMProcess):
         self._max_delayed_calls = max_delayed_calls  # kept for the signature: the directions are one device call, not Dask tasks
         self._use_relative_camera_poses = use_relative_camera_poses
         self._use_all_tracks_for_averaging = use_all_tracks_for_averaging
+        if translation_recovery == "device":
+            translation_recovery = device_translation_recovery
         self._translation_recovery = translation_recovery or default_translation_recovery
+        self._recovery_options: Dict[str, Any] = {}  # keys of the recovery engine's DEFAULTS, for the device's recovery
         self._device = device
         self._engine = None
         np.random.seed(0)
@@ -315,6 +374,26 @@ class TranslationAveraging1DSFM(GTSFMProcess):
             res["position"] = out["position"].cpu().numpy()
         return res
 
+    def recover_arrays(self, pair_images, world_pair, track_off=None, image=None, world_meas=None, pair_enable=None, meas_enable=None, num_images: Optional[int] = None,
+                       anchor: int = -1, scale_factor: float = 1.0, **options) -> Dict[str, Any]:
+        """``TranslationRecovery`` over arrays, beside ``compute_inliers_arrays``: the pair rows with their world directions, the tracks as CSR
+        with theirs, the two masks (normally ``pair_inlier`` / ``meas_inlier``). Returns host arrays ``translation`` [N + T, 3] (cameras, then
+        landmarks; NaN outside the anchor's component), ``node_valid``, and ``status``, ``counters``, ``costs``."""
+        from gtsfm_amd.runtime.translation_recovery_engine import COST_FIELDS, COUNTER_FIELDS
+
+        pairs = np.asarray(pair_images, np.int32).reshape(-1, 2)
+        image = np.zeros(0, np.int32) if image is None else np.asarray(image, np.int32)
+        if num_images is None:
+            num_images = int(max(pairs.max(initial=-1), image.max(initial=-1))) + 1
+        eng = recovery_engine(self._device)
+        dev = eng.upload(pairs, world_pair, pair_enable, np.zeros(1, np.int64) if track_off is None else track_off, image, np.zeros((0, 3)) if world_meas is None else world_meas,
+                         meas_enable)
+        opts = dict(sigma=NOISE_MODEL_SIGMA, huber_k=HUBER_LOSS_K if self._robust_measurement_noise else 0.0)
+        opts.update(getattr(self, "_recovery_options", {}), **options)
+        out = eng.recover(*dev, num_images=num_images, anchor=anchor, scale_factor=scale_factor, **opts)
+        return {"translation": out["translation"][0].cpu().numpy(), "node_valid": out["node_valid"][0].cpu().numpy(), "status": out["status"][0],
+                "counters": dict(zip(COUNTER_FIELDS, (int(x) for x in out["counters"][0]))), "costs": dict(zip(COST_FIELDS, (float(x) for x in out["costs"][0])))}
+
     @staticmethod
     def _dicts_to_arrays(w_i2Ui1_dict: Dict[Pair, Any], w_iUj_dict_tracks: Dict[Pair, Any]):  # noqa: N803
         pair_keys, meas_keys = list(w_i2Ui1_dict), list(w_iUj_dict_tracks)
@@ -373,8 +452,9 @@ class TranslationAveraging1DSFM(GTSFMProcess):
     def run_translation_averaging(self, num_images: int, i2Ui1_dict: Dict[Pair, Any], wRi_list: List[Any], tracks_2d: Optional[List[Any]] = None,  # noqa: N803
                                   intrinsics: Optional[List[Any]] = None, absolute_pose_priors: Sequence[Any] = (), i2Ti1_priors: Optional[Dict[Pair, Any]] = None,
                                   scale_factor: float = 1.0, gt_wTi_list: Sequence[Any] = ()):
-        """World-frame measurements, track selection, landmark directions, outlier rejection on the device, then ``translation_recovery``.
-        Returns (wTi_list, None, the inlier pairs); wTi is (wRi as a 3 x 3 array, wti) or None. The metrics group is out of scope."""
+        """World-frame measurements, track selection, landmark directions, outlier rejection on the device, then ``translation_recovery``
+        (on the device too with ``translation_recovery="device"``). Returns (wTi_list, None, the inlier pairs); wTi is (wRi as a 3 x 3
+        array, wti) or None. The metrics group is out of scope."""
         w_i2Ui1_dict, valid_cameras = get_valid_measurements_in_world_frame(i2Ui1_dict, wRi_list)
         if not self._use_relative_camera_poses:
             w_i2Ui1_dict = {}
@@ -391,8 +471,9 @@ class TranslationAveraging1DSFM(GTSFMProcess):
             inlier_pairs, inlier_tracks, _ = self.compute_inliers(w_i2Ui1_dict, w_iUj_dict_tracks)
         else:
             inlier_pairs, inlier_tracks = w_i2Ui1_dict, w_iUj_dict_tracks
+        extra = dict(device=self._device, **self._recovery_options) if self._translation_recovery is device_translation_recovery else {}
         wti_list = self._translation_recovery(num_images, inlier_pairs, inlier_tracks, wRi_list, i2Ti1_priors or {}, list(absolute_pose_priors), scale_factor,
-                                              self._robust_measurement_noise)
+                                              self._robust_measurement_noise, **extra)
         wTi_list = [(matrix3(r), np.asarray(t, np.float64).reshape(3)) if r is not None and t is not None else None for r, t in zip(wRi_list, wti_list)]  # noqa: N806
         return wTi_list, None, list(inlier_pairs.keys())
 

@@ -282,13 +282,47 @@ class VerifiedScene:
         call, which downloads the world directions. Edges of ``extra`` take part with their uploaded directions. Returns a
         ``TranslationInliers``: ``.edges`` (the inlier pairs: the ``edges=`` argument of ``tracks()`` and ``triangulate()``),
         ``.inlier_cameras``, ``.mean_weights``."""
+        return self._translation_inliers_on_device(wRi_list, camera_intrinsics, edges, averaging)[0]
+
+    def translation_averaging(self, wRi_list: List[Any], camera_intrinsics: List[Any], edges: Optional[Iterable[Tuple[int, int]]] = None, averaging=None,  # noqa: N803
+                              scale_factor: float = 1.0):
+        """Translation averaging for the scene's edges (``gtsfm/multi_view_optimizer.py``: ``TranslationAveraging1DSFM.run_translation_averaging``):
+        the outlier rejection of ``translation_inliers``, then the recovery (``gtsfm_translation_recovery_f64``) on the rejection's device
+        outputs where they lie -- the world directions, the two inlier masks, the pair rows and the track CSR; no direction is downloaded.
+        With ``averaging._reject_outliers`` off every valid row takes part. Positions, mask, counters and costs come back. Returns a
+        ``TranslationAverages``: ``.wti_list``, ``.wTi_list``, ``.cameras(intrinsics)`` for ``triangulate``, ``.landmarks``, ``.inliers``."""
+        from gtsfm_amd.averaging.translation.averaging_1dsfm import HUBER_LOSS_K, NOISE_MODEL_SIGMA, TranslationAveraging1DSFM, TranslationAverages, recovery_engine
+        from gtsfm_amd.runtime.translation_recovery_engine import COST_FIELDS, COUNTER_FIELDS
+
+        averaging = averaging or TranslationAveraging1DSFM(translation_recovery="device")
+        inliers, rows = self._translation_inliers_on_device(wRi_list, camera_intrinsics, edges, averaging)
+        num_images = 0 if self.feats is None else int(self.feats["xy"].shape[0])
+        rotations = [wRi_list[i] if i < len(wRi_list) else None for i in range(num_images)]
+        if rows is None:
+            return TranslationAverages(rotations, [None] * num_images, np.zeros((0, 3)), inliers, "NO_VALID_ROW", dict.fromkeys(COUNTER_FIELDS, 0),
+                                       dict.fromkeys(COST_FIELDS, float("nan")))
+        if not averaging._reject_outliers:  # a row that is not valid carries NaN directions: it stays out without a mask
+            rows = dict(rows, pair_enable=None, meas_enable=None)
+        opts = dict(sigma=NOISE_MODEL_SIGMA, huber_k=HUBER_LOSS_K if averaging._robust_measurement_noise else 0.0)
+        opts.update(getattr(averaging, "_recovery_options", {}))
+        out = recovery_engine(self.feats["xy"].device).recover(rows["pair_images"], rows["world_pair"], rows["pair_enable"], rows["track_off"], rows["image"], rows["world_meas"],
+                                                               rows["meas_enable"], num_images=num_images, scale_factor=scale_factor, **opts)
+        x, valid = out["translation"][0].cpu().numpy(), out["node_valid"][0].cpu().numpy()
+        wti = [x[i].copy() if valid[i] and rotations[i] is not None else None for i in range(num_images)]
+        return TranslationAverages(rotations, wti, x[num_images:].copy(), inliers, out["status"][0], dict(zip(COUNTER_FIELDS, (int(v) for v in out["counters"][0]))),
+                                   dict(zip(COST_FIELDS, (float(v) for v in out["costs"][0]))), rows)
+
+    def _translation_inliers_on_device(self, wRi_list, camera_intrinsics, edges, averaging):  # noqa: N803
+        """The body of ``translation_inliers``: (the ``TranslationInliers``, the rows as they lie on the device for the recovery: ``pair_images``,
+        ``world_pair``, ``pair_enable`` = the inlier mask, ``track_off``, ``image``, ``world_meas``, ``meas_enable`` = the inlier mask; None
+        for an empty scene)."""
         from gtsfm_amd.averaging.translation.averaging_1dsfm import TranslationAveraging1DSFM, TranslationInliers, matrix3, select_tracks_csr, vector3
         from gtsfm_amd.common.calibration import pinhole_parameters
         from gtsfm_amd.runtime.translation_engine import COUNT_FIELDS
 
         averaging = averaging or TranslationAveraging1DSFM()
         if self.feats is None:
-            return TranslationInliers([], np.zeros(0), np.zeros(0, np.uint8), np.zeros(0, np.uint8), np.zeros(0), np.zeros(0, np.uint8), dict.fromkeys(COUNT_FIELDS, 0))
+            return TranslationInliers([], np.zeros(0), np.zeros(0, np.uint8), np.zeros(0, np.uint8), np.zeros(0), np.zeros(0, np.uint8), dict.fromkeys(COUNT_FIELDS, 0)), None
         import torch
 
         xy = self.feats["xy"]
@@ -350,8 +384,10 @@ class VerifiedScene:
             directions = averaging.sample_projection_directions(combined[np.isfinite(combined).all(axis=1)])
         out = engine.inliers(*args, up(np.asarray(directions, np.float64).reshape(-1, 3)), threshold=averaging._outlier_weight_threshold, world=world, node_capacity=capacity)
         tracks = {"track_off": track_off_host, "image": image_host, "track_enable": track_enable, "meas_enable": meas_enable}
+        rows = {"pair_images": args[0], "world_pair": out["world_pair"], "pair_enable": out["pair_inlier"], "track_off": track_off, "image": image,
+                "world_meas": out["world_meas"], "meas_enable": out["meas_inlier"]}
         return TranslationInliers(pairs, out["pair_weight"].cpu().numpy(), out["pair_inlier"].cpu().numpy(), out["camera_inlier"].cpu().numpy(),
-                                  out["meas_weight"].cpu().numpy(), out["meas_inlier"].cpu().numpy(), out["counts"], tracks)
+                                  out["meas_weight"].cpu().numpy(), out["meas_inlier"].cpu().numpy(), out["counts"], tracks), rows
 
     def tracks(self, edges: Optional[Iterable[Tuple[int, int]]] = None) -> Dict[str, Any]:
         """The feature tracks of the verified correspondences (of ``edges`` only, when given: ``filter_corr_by_idx`` followed by

@@ -817,7 +817,7 @@ int gtsfm_largest_component(const int32_t* pair_images_dev, const uint8_t* pair_
  * Refused (GTSFM_ERR_INVALID, gtsfm_last_error): an enabled pair row with i1 >= i2 or an id out of range, a measurement listed twice, an
  * enabled measurement whose camera is out of range or has no valid rotation, D <= 0 with rows present.
  * PARITY UNPINNED towards the reference: gtsam's MFAS picks among several roots or tied scores in the order of an unordered_map; Unit3's
- * normalisation in the last bits; calibrations with distortion (not handled); TranslationRecovery (not part of this call).
+ * normalisation in the last bits; calibrations with distortion (not handled). TranslationRecovery is the next call, gtsfm_translation_recovery_f64.
  * ---------------------------------------------------------------------------------------------------------- */
 
 /* Bytes of device workspace (0 for sizes out of range). node_capacity: the most nodes that may have an edge (at most num_images +
@@ -887,6 +887,60 @@ int gtsfm_rotation_averaging_f64(const int32_t* pair_images_dev, const double* r
                                  double chordal_tol, int chordal_max_iterations, double delta0, double kappa_cg, double theta, double gradient_tol,
                                  int max_outer, int max_inner, void* workspace_dev, size_t workspace_bytes, double* rotation_out_dev,
                                  uint8_t* node_valid_dev, int32_t* counters_dev, double* costs_dev, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------
+ * Translation averaging, second half: translation recovery (float64)
+ *   replaces gtsfm/averaging/translation/averaging_1dsfm.py:439-495 (__run_averaging: gtsam's TranslationRecovery over the inlier
+ *   measurements, sigma 0.01, Huber k = 1.3), called from gtsfm/multi_view_optimizer.py right after the outlier rejection.
+ * The inputs are the arrays gtsfm_translation_inliers_f64 takes and leaves on the device. Camera i is node i, track j of a problem whose
+ * first track is t0 is node num_images + (j - t0) (num_images + j for a single problem). A pair row (i1, i2) with the world direction z =
+ * w_i2Ui1 (world_pair_dev [E][3]) is the measurement a = i2, b = i1; measurement s of track j (track_off_dev [T + 1], image_dev [S],
+ * world_meas_dev [S][3]) is a = image[s], b = the track's node; the model is unit(x_b - x_a) = z. A row is VALID when it is enabled
+ * (pair_enable_dev / meas_enable_dev, normally the 1DSfM inlier masks; NULL: every row) and its three numbers are finite. Refused
+ * (GTSFM_ERR_INVALID, gtsfm_last_error, no output written): an enabled pair with i1 >= i2, an enabled row with an image outside
+ * 0 .. num_images - 1, track or problem offsets that are not ascending within their range, a problem with more than max_problem_tracks tracks.
+ * The cost is f(x) = sum_e rho(|unit(x_b - x_a) - z_e| / sigma) with Huber's rho (huber_k <= 0 or inf: the half square), plus one SCALE ROW
+ * rho(|(x_b - x_a) - scale_factor z| / sigma) on the first valid row of the solved component. The gauge is hard: x_anchor = 0 exactly, the
+ * anchor is not an unknown; anchor = -1 takes the a of the first valid row (measurements[0].key1()). Only the anchor's connected component
+ * over the valid rows is solved; every other node gets NaN and node_valid 0.
+ * A. Initialisation: min sum_e |x_b - x_a - scale_factor z_e|^2, x_anchor = 0: the scalar graph Laplacian with three right-hand sides, by
+ * conjugate gradients from x = 0 (one step length) to |r| <= init_tol |r0| or init_max_iterations. B. Trust region on the Gauss-Newton
+ * model with the Huber weights w = min(1, k sigma / |r|): gradient sum +- w P_u r / (|d| sigma^2), Hessian sum +- w P_u (v_b - v_a) /
+ * (|d| sigma)^2, P_u = I - u u^T, plus the scale row's w / sigma^2; Steihaug-Toint truncated CG preconditioned by the scalar per-node
+ * Jacobi weight m_i = (2 sum w / (|d| sigma)^2 + 3 w_scale / sigma^2) / 3, the radius delta0 measured in that M-norm; the inner loop ends at
+ * |r|_M^-1 <= kappa_cg |r0|_M^-1, on the boundary or after max_inner steps (0: three per node); accept at rho > 0.1, Delta / 4 under 0.25,
+ * Delta * 2 above 0.75 on the boundary, rho regularised as in the rotation call. The outer loop ends when an accepted step lowers the cost
+ * by at most rel_tol * f or abs_tol, at |g|_inf <= gradient_tol / sigma^2 (both CONVERGED), or after max_outer iterations. A row with
+ * |x_b - x_a| = 0 at the point held gives NaN and the problem ends NON_FINITE. Sums run over a node's rows in ascending (neighbour, row)
+ * order (a problem's rows: its pairs, then its measurements) and over the nodes by a fixed pairwise tree, so every byte is fixed by the
+ * inputs: not by the lane count, the run, or the problem's place in a batch. The specification is
+ * tests/translation_recovery_reference.py, operation for operation.
+ * Batch: problem_row_off_dev [P + 1][2] int64 = (first pair row, first track) per problem (NULL with num_problems 1 and max_problem_tracks
+ * = num_tracks: one problem over everything); one workgroup solves one problem.
+ * PARITY UNPINNED towards the reference (nothing of gtsam was observed running): gtsam's Levenberg-Marquardt path and its seeded random
+ * start (here a deterministic linear start); its soft prior on the first key (here a hard anchor); Unit3 and the 2-dimensional noise model
+ * of the reference's gtsam version (here the 3-vector chordal residual with the same sigma); relative and absolute pose priors;
+ * rig_1dsfm.py; the metrics group. The point returned is a critical point reached from the linear start: no local-minimum guarantee.
+ * ---------------------------------------------------------------------------------------------------------- */
+
+/* Bytes of device workspace (0 for sizes out of range: negative, 2^28 rows, 2^24 nodes, 2^28 nodes over all problems, max_problem_tracks >
+ * num_tracks): about 105 per row and 300 per node and problem, nodes = num_images + max_problem_tracks. One workgroup solves one problem,
+ * start to end, as in the rotation call: a call's time grows with rows x steps on ONE CU. */
+size_t gtsfm_translation_recovery_workspace_bytes(long long num_pairs, long long num_meas, long long num_images, long long num_tracks,
+                                                  long long max_problem_tracks, long long num_problems);
+
+/* Outputs per problem, M = num_images + max_problem_tracks: translation_out_dev [P][M][3] (NaN outside the component), node_valid_dev [P][M]
+ * uint8, counters_dev [P][8] int32 = status (0 CONVERGED, 1 MAX_ITERATIONS, 2 NO_VALID_ROW: all outputs NaN / 0, 3 NON_FINITE: outputs NaN,
+ * mask 0), outer iterations, accepted steps, Hessian applications, initialisation CG steps, component size, anchor, valid rows; costs_dev
+ * [P][4] float64 = the cost at the initialisation, the final cost, the final |g|_inf, the trust radius at exit. The call waits for the
+ * stream once, for the two refusal flags; the inputs are not changed. */
+int gtsfm_translation_recovery_f64(const int32_t* pair_images_dev, const double* world_pair_dev, const uint8_t* pair_enable_dev, long long num_pairs,
+                                   const long long* track_off_dev, const int32_t* image_dev, const double* world_meas_dev, const uint8_t* meas_enable_dev,
+                                   long long num_tracks, long long num_meas, int num_images, const long long* problem_row_off_dev, int num_problems,
+                                   long long max_problem_tracks, int anchor, double scale_factor, double sigma, double huber_k, double init_tol,
+                                   int init_max_iterations, double delta0, double kappa_cg, double gradient_tol, double rel_tol, double abs_tol, int max_outer,
+                                   int max_inner, void* workspace_dev, size_t workspace_bytes, double* translation_out_dev, uint8_t* node_valid_dev,
+                                   int32_t* counters_dev, double* costs_dev, void* stream);
 
 #ifdef __cplusplus
 }
