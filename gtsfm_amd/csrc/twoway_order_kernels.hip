@@ -11,7 +11,7 @@
 //                     atomic on the output and no workspace; the slots are a permutation of 0 .. K-1 by construction, so
 //                     the result does not depend on the grid or on timing. Rows that are not kept carry the all-ones key,
 //                     which is below nothing.
-//   pack_rows_kernel: float32 rows holding the integers 0 .. 255 (SIFT descriptors as OpenCV emits them) -> uint8 rows;
+//   pack_rows_u8_kernel: float32 rows holding the integers 0 .. 255 (SIFT descriptors as OpenCV emits them) -> uint8 rows;
 //                     any other value writes 0 and raises a flag, nothing is clamped.
 
 #include "../../include/gtsfm_amd.h"
@@ -76,7 +76,7 @@ __global__ __launch_bounds__(TWO_ROWS) void tw_order_kernel(const int* __restric
     }
 }
 
-__global__ __launch_bounds__(256) void pack_rows_kernel(const float* __restrict__ src, long long rows, int dim, int src_stride,
+__global__ __launch_bounds__(256) void pack_rows_u8_kernel(const float* __restrict__ src, long long rows, int dim, int src_stride,
                                                         uint8_t* __restrict__ dst, int dst_stride, int* __restrict__ flag) {
     const long long total = rows * dim;
     bool bad = false;
@@ -112,8 +112,8 @@ extern "C" int gtsfm_pack_rows_f32_to_u8(const float* src_dev, long long rows, i
     GTSFM_CHECK_ARG(src_dev && dst_dev && flag_dev, "pack_rows_f32_to_u8: null pointer");
     if (rows == 0) return GTSFM_OK;
     const long long blocks = (rows * dim + 255) / 256;
-    hipLaunchKernelGGL(pack_rows_kernel, dim3((unsigned)(blocks < 65536 ? blocks : 65536)), dim3(256), 0, (hipStream_t)stream, src_dev, rows, dim,
+    hipLaunchKernelGGL(pack_rows_u8_kernel, dim3((unsigned)(blocks < 65536 ? blocks : 65536)), dim3(256), 0, (hipStream_t)stream, src_dev, rows, dim,
                        src_stride, dst_dev, dst_stride, flag_dev);
-    GTSFM_CHECK_LAUNCH("pack_rows_kernel");
+    GTSFM_CHECK_LAUNCH("pack_rows_u8_kernel");
     return GTSFM_OK;
 }

@@ -1,4 +1,4 @@
-"""CPU: the translation-recovery solver itself (tr_validate and tr_solve of gtsfm_amd/csrc/translation_recovery_kernels.hip, the functions the
+"""CPU: the translation-recovery solver itself (trec_validate and trec_solve of gtsfm_amd/csrc/translation_recovery_kernels.hip, the functions the
 kernels run), compiled for the host into the stand-alone program tools/translation_recovery_host_main.cpp -- once plain and once with the
 host's address and undefined-behaviour sanitizers -- on every scene of tests/translation_recovery_scenes.py. The program solves each scene
 with one lane over zeroed memory and with the device's 256-lane partition, last lane first, over memory filled with 0xFF, and every problem

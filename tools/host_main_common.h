@@ -73,4 +73,18 @@ bool same(const std::vector<T>& a, const std::vector<T>& b) {
     return a.size() == b.size() && (a.empty() || memcmp(a.data(), b.data(), a.size() * sizeof(T)) == 0);
 }
 
+// `one` equals the elements of `all` from `at` on
+template <class T>
+bool same_slice(const std::vector<T>& all, size_t at, const std::vector<T>& one) {
+    return one.empty() || memcmp(all.data() + at, one.data(), one.size() * sizeof(T)) == 0;
+}
+
+// n elements in an allocation of their exact size
+template <class T>
+T* copy_of(const T* from, size_t n) {
+    T* p = (T*)malloc(n ? n * sizeof(T) : 1);
+    if (n) memcpy(p, from, n * sizeof(T));
+    return p;
+}
+
 }  // namespace

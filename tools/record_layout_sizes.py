@@ -67,6 +67,13 @@ def cases() -> Dict[str, List[list]]:
     for name in ("gtsfm_sg_workspace_bytes", "gtsfm_lg_workspace_bytes", "gtsfm_sinkhorn_workspace_bytes", "gtsfm_lg_assignment_workspace_bytes"):
         c[name] = [[0, [], []], [-1, [1], [1]]] + [[len(a), a, b] for a, b in pairs]
     c["gtsfm_score_matrices_workspace_bytes"] = [[0], [-1], [1], [2], [3], [7], [8], [9], [16], [32], [1000]]
+    # (rows, images, problems): refused, no rows, no images, both sides of the 256-byte roundings (64 ints, 256 validity bytes), batches
+    c["gtsfm_rotation_averaging_workspace_bytes"] = [[-1, 4, 1], [4, 4, 0], [0, 0, 1], [0, 5, 1], [7, 0, 1], [1, 2, 1], [32, 62, 1], [33, 63, 1], [256, 64, 1], [257, 65, 3],
+                                                     [1035, 46, 1], [1035, 46, 64], [48725, 1000, 1]]
+    # (pairs, measurements, images, tracks, the most tracks of a problem, problems); more tracks per problem than tracks is refused
+    c["gtsfm_translation_recovery_workspace_bytes"] = [[-1, 0, 4, 0, 0, 1], [4, 4, 4, 2, 3, 1], [0, 0, 0, 0, 0, 1], [0, 0, 5, 0, 0, 1], [3, 0, 0, 0, 0, 1], [0, 6, 4, 2, 2, 1],
+                                                       [1, 0, 2, 0, 0, 1], [20, 12, 40, 22, 22, 1], [20, 13, 40, 23, 23, 1], [200, 57, 30, 35, 9, 4], [256, 0, 64, 0, 0, 3],
+                                                       [1035, 552, 46, 184, 184, 1], [1035, 552, 46, 184, 3, 64], [48725, 12000, 1000, 4000, 4000, 1]]
     return c
 
 

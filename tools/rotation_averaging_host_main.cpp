@@ -70,7 +70,7 @@ int run(const Scene& s, int lanes, bool descending, int fill, Outputs& out) {
     RaArgs a{s.pair_images, s.rotation, s.weight, s.has_enable ? s.pair_enable : nullptr, s.row_off, s.E, (int)s.N, (int)s.P, (int)s.anchor, s.chordal_tol, s.delta0,
              s.kappa_cg, s.theta, s.gradient_tol, (int)s.chordal_cap, (int)s.max_outer, (int)s.max_inner, ra_layout(ws, s.E, s.N, s.P), out.wri.data(),
              out.node_valid.data(), out.counters.data(), out.costs.data()};
-    for (int i = 0; i < RA_FLAG_WORDS; ++i) a.w.flags[i] = 0;
+    for (int i = 0; i < SOLVER_FLAG_WORDS; ++i) a.w.flags[i] = 0;
     const long long n = s.E > s.P ? s.E : s.P;
     for (long long k = 0; k < n; ++k) ra_validate(a, descending ? n - 1 - k : k);
     if (a.w.flags[0] || a.w.flags[1]) {
@@ -78,15 +78,10 @@ int run(const Scene& s, int lanes, bool descending, int fill, Outputs& out) {
         free(ws);
         return 3;
     }
-    ra_host.lanes = lanes, ra_host.descending = descending ? 1 : 0;
+    solver_host.lanes = lanes, solver_host.descending = descending ? 1 : 0;
     for (long long k = 0; k < s.P; ++k) ra_solve(a, (int)(descending ? s.P - 1 - k : k));
     free(ws);
     return 0;
-}
-
-template <class T>
-bool same_slice(const std::vector<T>& all, size_t at, const std::vector<T>& one) {
-    return one.empty() || memcmp(all.data() + at, one.data(), one.size() * sizeof(T)) == 0;
 }
 
 }  // namespace
@@ -103,21 +98,17 @@ int main(int argc, char** argv) {
     }
     Outputs first, second;
     int rc = run(s, 1, false, 0x00, first);
-    if (rc == 0) rc = run(s, RA_THREADS, true, 0xFF, second);
+    if (rc == 0) rc = run(s, SOLVER_THREADS, true, 0xFF, second);
     if (rc == 0 && !(same(first.wri, second.wri) && same(first.node_valid, second.node_valid) && same(first.counters, second.counters) && same(first.costs, second.costs))) {
-        fprintf(stderr, "one lane and %d lanes differ\n", RA_THREADS);
+        fprintf(stderr, "one lane and %d lanes differ\n", SOLVER_THREADS);
         rc = 2;
     }
     for (long long p = 0; rc == 0 && s.P > 1 && p < s.P; ++p) {  // the problem alone: its rows only, copied to arrays of their exact size
         const long long lo = s.row_off[p], count = s.row_off[p + 1] - lo;
         Scene one = s;
         one.E = count, one.P = 1;
-        one.pair_images = (int*)malloc(count ? 2 * count * sizeof(int) : 1), one.rotation = (double*)malloc(count ? 9 * count * 8 : 1);
-        one.weight = (double*)malloc(count ? count * 8 : 1), one.pair_enable = (uint8_t*)malloc(count ? count : 1), one.row_off = (long long*)malloc(16);
-        if (count) {
-            memcpy(one.pair_images, s.pair_images + 2 * lo, 2 * count * sizeof(int)), memcpy(one.rotation, s.rotation + 9 * lo, 9 * count * 8);
-            memcpy(one.weight, s.weight + lo, count * 8), memcpy(one.pair_enable, s.pair_enable + lo, count);
-        }
+        one.pair_images = copy_of(s.pair_images + 2 * lo, 2 * count), one.rotation = copy_of(s.rotation + 9 * lo, 9 * count);
+        one.weight = copy_of(s.weight + lo, count), one.pair_enable = copy_of(s.pair_enable + lo, count), one.row_off = (long long*)malloc(16);
         one.row_off[0] = 0, one.row_off[1] = count;
         Outputs alone;
         rc = run(one, 64, false, 0x55, alone);  // a third lane count

@@ -1,4 +1,4 @@
-// Stand-alone host build of the translation-recovery solver (gtsfm_amd/csrc/translation_recovery_kernels.hip: tr_validate and tr_solve, the
+// Stand-alone host build of the translation-recovery solver (gtsfm_amd/csrc/translation_recovery_kernels.hip: trec_validate and trec_solve, the
 // very functions the kernels run), for running it on a CPU and under the host sanitizers:
 //
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off [-Xarch_host -fsanitize=address,undefined] -c tools/translation_recovery_host_main.cpp -o main.o
@@ -39,7 +39,7 @@ bool read_scene(const char* path, Scene& s) {
     if (!f) return false;
     long long head[16];
     double opts[16];
-    bool ok = fread(head, 8, 16, f) == 16 && fread(opts, 8, 16, f) == 16 && head[0] == SCENE_MAGIC && tr_sizes_ok(head[1], head[3], head[4], head[2], head[6], head[5]);
+    bool ok = fread(head, 8, 16, f) == 16 && fread(opts, 8, 16, f) == 16 && head[0] == SCENE_MAGIC && trec_sizes_ok(head[1], head[3], head[4], head[2], head[6], head[5]);
     if (ok) {
         s.E = head[1], s.T = head[2], s.S = head[3], s.N = head[4], s.P = head[5], s.max_tracks = head[6], s.anchor = head[7], s.init_cap = head[8], s.max_outer = head[9];
         s.max_inner = head[10];
@@ -69,39 +69,27 @@ int run(const Scene& s, int lanes, bool descending, int fill, Outputs& out) {
     const size_t P = s.P, M = s.N + s.max_tracks;
     fill_vector(out.translation, P * M * 3, fill), fill_vector(out.node_valid, P * M, fill), fill_vector(out.counters, P * 8, fill), fill_vector(out.costs, P * 4, fill);
     if (!(s.anchor >= -1 && (s.anchor < (long long)M || s.anchor == -1)) ||
-        !tr_options_ok(s.scale, s.sigma, s.huber_k, s.init_tol, (int)s.init_cap, s.delta0, s.kappa_cg, s.gradient_tol, s.rel_tol, s.abs_tol, (int)s.max_outer, (int)s.max_inner)) {
+        !trec_options_ok(s.scale, s.sigma, s.huber_k, s.init_tol, (int)s.init_cap, s.delta0, s.kappa_cg, s.gradient_tol, s.rel_tol, s.abs_tol, (int)s.max_outer, (int)s.max_inner)) {
         fprintf(stderr, "refused: the anchor or an option\n");
         return 3;
     }
-    const size_t bytes = tr_layout(nullptr, s.E, s.S, (long long)M, s.P).bytes;
+    const size_t bytes = trec_layout(nullptr, s.E, s.S, (long long)M, s.P).bytes;
     void* ws = filled(bytes, fill);
-    TrArgs a{s.pair_images, s.world_pair, s.pair_enable, s.track_off, s.image, s.world_meas, s.meas_enable, s.row_off, s.E, s.T, s.S, (int)s.N, (int)s.max_tracks, (int)s.P,
-             (int)s.anchor, s.scale, s.sigma, s.huber_k, s.init_tol, s.delta0, s.kappa_cg, s.gradient_tol, s.rel_tol, s.abs_tol, (int)s.init_cap, (int)s.max_outer,
-             (int)s.max_inner, tr_layout(ws, s.E, s.S, (long long)M, s.P), out.translation.data(), out.node_valid.data(), out.counters.data(), out.costs.data()};
-    for (int i = 0; i < TR_FLAG_WORDS; ++i) a.w.flags[i] = 0;
-    const long long n = tr_validate_lanes(s.E, s.S, s.T, s.P);
-    for (long long k = 0; k < n; ++k) tr_validate(a, descending ? n - 1 - k : k);
+    TrecArgs a{s.pair_images, s.world_pair, s.pair_enable, s.track_off, s.image, s.world_meas, s.meas_enable, s.row_off, s.E, s.T, s.S, (int)s.N, (int)s.max_tracks, (int)s.P,
+               (int)s.anchor, s.scale, s.sigma, s.huber_k, s.init_tol, s.delta0, s.kappa_cg, s.gradient_tol, s.rel_tol, s.abs_tol, (int)s.init_cap, (int)s.max_outer,
+               (int)s.max_inner, trec_layout(ws, s.E, s.S, (long long)M, s.P), out.translation.data(), out.node_valid.data(), out.counters.data(), out.costs.data()};
+    for (int i = 0; i < SOLVER_FLAG_WORDS; ++i) a.w.flags[i] = 0;
+    const long long n = trec_validate_lanes(s.E, s.S, s.T, s.P);
+    for (long long k = 0; k < n; ++k) trec_validate(a, descending ? n - 1 - k : k);
     if (a.w.flags[0] || a.w.flags[1]) {
         fprintf(stderr, "refused: %s\n", a.w.flags[0] ? "a bad pair or measurement" : "bad track or problem offsets");
         free(ws);
         return 3;
     }
-    tr_host.lanes = lanes, tr_host.descending = descending ? 1 : 0;
-    for (long long k = 0; k < s.P; ++k) tr_solve(a, (int)(descending ? s.P - 1 - k : k));
+    solver_host.lanes = lanes, solver_host.descending = descending ? 1 : 0;
+    for (long long k = 0; k < s.P; ++k) trec_solve(a, (int)(descending ? s.P - 1 - k : k));
     free(ws);
     return 0;
-}
-
-template <class T>
-bool same_slice(const std::vector<T>& all, size_t at, const std::vector<T>& one) {
-    return one.empty() || memcmp(all.data() + at, one.data(), one.size() * sizeof(T)) == 0;
-}
-
-template <class T>
-T* copy_of(const T* from, size_t n) {
-    T* p = (T*)malloc(n ? n * sizeof(T) : 1);
-    if (n) memcpy(p, from, n * sizeof(T));
-    return p;
 }
 
 }  // namespace
@@ -118,10 +106,10 @@ int main(int argc, char** argv) {
     }
     Outputs first, second;
     int rc = run(s, 1, false, 0x00, first);
-    if (rc == 0) rc = run(s, TR_THREADS, true, 0xFF, second);
+    if (rc == 0) rc = run(s, SOLVER_THREADS, true, 0xFF, second);
     if (rc == 0 && !(same(first.translation, second.translation) && same(first.node_valid, second.node_valid) && same(first.counters, second.counters) &&
                      same(first.costs, second.costs))) {
-        fprintf(stderr, "one lane and %d lanes differ\n", TR_THREADS);
+        fprintf(stderr, "one lane and %d lanes differ\n", SOLVER_THREADS);
         rc = 2;
     }
     const size_t M = s.N + s.max_tracks;
