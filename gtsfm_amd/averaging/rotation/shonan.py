@@ -43,6 +43,13 @@ class RotationAverages:
         self.wRi_list, self.status, self.counters, self.costs = wRi_list, status, counters, costs  # noqa: N815
         self.pairs, self.weight, self.enabled = pairs, weight, enabled
 
+    @classmethod
+    def empty(cls) -> "RotationAverages":
+        """The result for a scene without rows."""
+        from gtsfm_amd.runtime.rotation_averaging_engine import COST_FIELDS, COUNTER_FIELDS
+
+        return cls([], "NO_VALID_ROW", dict.fromkeys(COUNTER_FIELDS, 0), dict.fromkeys(COST_FIELDS, float("nan")), [], np.zeros(0), np.zeros(0, np.uint8))
+
 
 class ShonanRotationAveraging(RotationAveragingBase):
     """Performs rotation averaging on Shonan's chordal cost at p = 3."""

@@ -218,6 +218,13 @@ class TranslationAverages:
         self.status, self.counters, self.costs, self._device_rows = status, counters, costs, device_rows
         self.wTi_list = [(matrix3(r), t) if r is not None and t is not None else None for r, t in zip(wRi_list, wti_list)]
 
+    @classmethod
+    def empty(cls, inliers: "TranslationInliers") -> "TranslationAverages":
+        """The result for a scene without rows."""
+        from gtsfm_amd.runtime.translation_recovery_engine import COST_FIELDS, COUNTER_FIELDS
+
+        return cls([], [], np.zeros((0, 3)), inliers, "NO_VALID_ROW", dict.fromkeys(COUNTER_FIELDS, 0), dict.fromkeys(COST_FIELDS, float("nan")))
+
     def cameras(self, intrinsics) -> Dict[int, Any]:
         """{image: PinholeCamera} of the images with a pose and a calibration: the ``cameras`` argument of ``triangulate``."""
         from gtsfm_amd.common.calibration import PinholeCamera
@@ -241,6 +248,13 @@ class TranslationInliers:
         self.edges = [p for p, k in zip(pairs, pair_inlier.tolist()) if k]
         self.inlier_cameras = set(np.flatnonzero(camera_inlier).tolist())
         self.mean_weights = {p: float(w) for p, w in zip(pairs, pair_weight.tolist())}
+
+    @classmethod
+    def empty(cls) -> "TranslationInliers":
+        """The result for a scene without rows."""
+        from gtsfm_amd.runtime.translation_engine import COUNT_FIELDS
+
+        return cls([], np.zeros(0), np.zeros(0, np.uint8), np.zeros(0, np.uint8), np.zeros(0), np.zeros(0, np.uint8), dict.fromkeys(COUNT_FIELDS, 0))
 
 
 class TranslationAveraging1DSFM(GTSFMProcess):

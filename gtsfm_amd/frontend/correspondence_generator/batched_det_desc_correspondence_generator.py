@@ -80,7 +80,7 @@ class BatchedDetDescCorrespondenceGenerator(CorrespondenceGeneratorBase):
         """``generate_correspondences_and_verify`` that also keeps the handles of what stayed in HBM: the returned ``VerifiedScene`` holds
         the same three objects and builds the scene's feature tracks on the device (``.tracks()`` / ``.tracks_2d()``)."""
         from gtsfm_amd.common.calibration import pinhole_parameters
-        from gtsfm_amd.frontend.verifier.ransac import Ransac, _to_pose_types
+        from gtsfm_amd.frontend.verifier.ransac import Ransac
 
         if not isinstance(verifier, Ransac):
             raise TypeError("generate_correspondences_and_verify needs gtsfm_amd's Ransac verifier")
@@ -92,7 +92,6 @@ class BatchedDetDescCorrespondenceGenerator(CorrespondenceGeneratorBase):
         keypoints_list, putative, state = self._detect_and_match(client, images, visibility_graph)
         params = [pinhole_parameters(c) for c in camera_intrinsics]
         use_intrinsics = bool(verifier._use_intrinsics_in_verification)
-        verified: Dict[Tuple[int, int], Tuple[Any, Any, np.ndarray, float]] = {}
         on_device = [r for r in state["results"]]
         if use_intrinsics and not all(p[4] for p in params):
             # distortion / skew / a non-pinhole model: those edges use the calibration's own calibrate(), per pair on the host,
@@ -103,22 +102,8 @@ class BatchedDetDescCorrespondenceGenerator(CorrespondenceGeneratorBase):
         if on_device:
             intr = np.array([p[:4] for p in params], dtype=np.float64)
             ver = state["pipe"].verify(state["feats"], on_device, intr, float(verifier._estimation_threshold_px), use_intrinsics=use_intrinsics)
-            for pair, res in state["pipe"].verified_to_numpy(ver).items():
-                dtype = putative[pair].dtype
-                if res["R"] is None:
-                    verified[pair] = verifier._failure_result
-                else:
-                    rot, direction = _to_pose_types(res["R"], res["t"])
-                    verified[pair] = (rot, direction, res["v_corr_idxs"].astype(dtype), res["inlier_ratio"])
-        extra: Dict[Tuple[int, int], np.ndarray] = {}
-        for pair in putative:
-            if pair not in verified:  # empty keypoint sets, or a calibration the device path does not model
-                i1, i2 = pair
-                per_pair = Ransac(use_intrinsics, verifier._estimation_threshold_px, seed=(i1 << 32) | i2)
-                per_pair._engine = verifier._ensure_engine()  # one lib handle / workspace for every fallback edge
-                verified[pair] = per_pair.verify(keypoints_list[i1], keypoints_list[i2], putative[pair], camera_intrinsics[i1], camera_intrinsics[i2])
-                extra[pair] = verified[pair][2]
-        return VerifiedScene(keypoints_list, putative, {p: verified[p] for p in putative}, state["feats"], ver, extra)
+        # the other edges (empty keypoint sets, or a calibration the device path does not model) go through the per-pair fallback
+        return VerifiedScene.from_launches(keypoints_list, putative, state["feats"], ver, {p for r in ver for p in r["pairs"]}, verifier, camera_intrinsics)
 
     def _detect_and_match(self, client: Any, images: List[Any], visibility_graph: List[Tuple[int, int]]):
         from gtsfm_amd.runtime.pipeline import FrontEndPipeline

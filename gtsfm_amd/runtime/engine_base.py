@@ -1,5 +1,6 @@
-"""What every single-workspace engine shares: the device, the library handle, one cached workspace that grows when a call needs more,
-and the host-or-device upload helper. An engine adds which size function it asks and what it raises when that function refuses."""
+"""What every single-workspace engine shares: the device, the library handle, one cached workspace that grows when a call needs more
+(sized by the size function an engine names), the check of the tensors a call is given, NULL for an absent or empty tensor, the
+current stream's handle and the upload helpers; and, for their results and options, counters by name and options over defaults."""
 
 from __future__ import annotations
 
@@ -20,6 +21,19 @@ _SLACK = {
     "pad": (lambda need: need + 256, False),
     "quarter": (lambda need: int(need * 1.25) + 256, False),  # engines whose batches vary from call to call
 }
+
+
+def named(row, fields, cast=int):
+    """One row of counters (or costs, with ``cast=float``) as a dict by ``fields``; spare columns past the names are dropped."""
+    return {k: cast(row[i]) for i, k in enumerate(fields)}
+
+
+def merge_options(defaults, options):
+    """``options`` over ``defaults``; a key that ``defaults`` does not have is a ``TypeError``, as an unknown keyword is."""
+    unknown = set(options) - set(defaults)
+    if unknown:
+        raise TypeError(f"unknown options {sorted(unknown)}")
+    return dict(defaults, **options)
 
 
 class EngineBase:
@@ -46,6 +60,33 @@ class EngineBase:
                 self._ws = None
             self._ws = self._torch.empty(size(need), dtype=self._torch.uint8, device=self.device)
         return self._ws
+
+    def _sized_workspace(self, size_fn: str, *sizes):
+        """The workspace, as large as the library's ``size_fn(*sizes)`` asks; 0 is its refusal of the sizes."""
+        need = int(getattr(self._lib, size_fn)(*sizes))
+        if need == 0:
+            raise ValueError(f"{size_fn} refuses {sizes}")
+        return self._grow(need)
+
+    def _check_tensors(self, rows, optional=()):
+        """Every ``(name, tensor, dtype, count)`` row is a contiguous device tensor of that dtype and size; a name in ``optional`` may be None."""
+        for name, x, dt, count in rows:
+            if x is None and name in optional:
+                continue
+            if not (isinstance(x, self._torch.Tensor) and x.is_cuda and x.dtype == dt and x.is_contiguous() and x.numel() == count):
+                raise TypeError(f"{name} must be a contiguous {dt} device tensor of {max(count, 0)} entries")
+
+    @staticmethod
+    def _ptr(x):
+        """The address of a tensor; NULL for None and for an empty one."""
+        return None if x is None or x.numel() == 0 else x.data_ptr()
+
+    def _stream(self) -> int:
+        return self._torch.cuda.current_stream(self.device).cuda_stream
+
+    def _up(self, a, np_dtype, shape):
+        """A host array on the device as a contiguous ``np_dtype`` tensor of ``shape``; None stays None. What every ``upload()`` is made of."""
+        return None if a is None else self._torch.from_numpy(np.ascontiguousarray(np.asarray(a, dtype=np_dtype).reshape(shape))).to(self.device)
 
     def _dev(self, a, dtype):
         """``a`` on the device as a contiguous ``dtype`` tensor: a tensor is converted where it lies, anything else goes up through numpy."""

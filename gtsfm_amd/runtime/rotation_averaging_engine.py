@@ -8,7 +8,7 @@ from typing import Dict, Optional
 
 import numpy as np
 
-from gtsfm_amd.runtime.engine_base import EngineBase
+from gtsfm_amd.runtime.engine_base import EngineBase, merge_options
 
 COUNTER_FIELDS = ("status", "outer_iterations", "accepted_steps", "hessian_applications", "chordal_cg_steps", "component_size", "anchor", "valid_rows")
 COST_FIELDS = ("initial_cost", "chordal_cost", "final_cost", "gradient_inf_norm")
@@ -19,12 +19,6 @@ DEFAULTS = dict(chordal_tol=1e-10, chordal_max_iterations=2000, delta0=1.0, kapp
 
 
 class RotationAveragingEngine(EngineBase):
-    def _workspace(self, *sizes):
-        need = int(self._lib.gtsfm_rotation_averaging_workspace_bytes(*sizes))
-        if need == 0:
-            raise ValueError(f"gtsfm_rotation_averaging_workspace_bytes refuses {sizes}")
-        return self._grow(need)
-
     def average(self, pair_images, rotation, weight, pair_enable=None, *, num_images: int, anchor: int = -1, problem_row_off=None, **options) -> Dict[str, object]:
         """Device tensors as in include/gtsfm_amd.h: ``pair_images`` [E, 2] int32 = (i1, i2), ``rotation`` [E, 9] float64 = i2Ri1, ``weight`` [E]
         float64, ``pair_enable`` [E] uint8 or None, ``problem_row_off`` [P + 1] int64 or None (one problem over every row). ``options``: the keys
@@ -32,41 +26,29 @@ class RotationAveragingEngine(EngineBase):
         [P, 4] float64 and ``status`` (a list of names). The inputs are not changed."""
         torch = self._torch
         dev = self.device
-        unknown = set(options) - set(DEFAULTS)
-        if unknown:
-            raise TypeError(f"unknown options {sorted(unknown)}")
-        o = dict(DEFAULTS, **options)
+        o = merge_options(DEFAULTS, options)
         e, n = int(pair_images.shape[0]), int(num_images)
         p = 1 if problem_row_off is None else int(problem_row_off.shape[0]) - 1
         if p < 1:
             raise ValueError("problem_row_off must be [P + 1] with P >= 1")
-        for name, x, dt, count in (("pair_images", pair_images, torch.int32, 2 * e), ("rotation", rotation, torch.float64, 9 * e), ("weight", weight, torch.float64, e),
-                                   ("pair_enable", pair_enable, torch.uint8, e), ("problem_row_off", problem_row_off, torch.int64, p + 1)):
-            if x is None and name in ("pair_enable", "problem_row_off"):
-                continue
-            if not (isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == dt and x.is_contiguous() and x.numel() == count):
-                raise TypeError(f"{name} must be a contiguous {dt} device tensor of {count} entries")
-        ws = self._workspace(e, n, p)
+        self._check_tensors((("pair_images", pair_images, torch.int32, 2 * e), ("rotation", rotation, torch.float64, 9 * e), ("weight", weight, torch.float64, e),
+                             ("pair_enable", pair_enable, torch.uint8, e), ("problem_row_off", problem_row_off, torch.int64, p + 1)), optional=("pair_enable", "problem_row_off"))
+        ws = self._sized_workspace("gtsfm_rotation_averaging_workspace_bytes", e, n, p)
         wri = torch.empty((p, n, 9), dtype=torch.float64, device=dev)
         node_valid = torch.empty((p, n), dtype=torch.uint8, device=dev)
         counters = torch.empty((p, 8), dtype=torch.int32, device=dev)
         costs = torch.empty((p, 4), dtype=torch.float64, device=dev)
-        ptr = self._L.ptr
-        q = lambda x: ptr(x) if x is not None and x.numel() else None  # noqa: E731
+        q = self._ptr
         rc = self._lib.gtsfm_rotation_averaging_f64(
             q(pair_images), q(rotation), q(weight), q(pair_enable), e, n, q(problem_row_off), p, int(anchor), float(o["chordal_tol"]), int(o["chordal_max_iterations"]),
             float(o["delta0"]), float(o["kappa_cg"]), float(o["theta"]), float(o["gradient_tol"]), int(o["max_outer"]), int(o["max_inner"]), ws.data_ptr(), ws.numel(),
-            q(wri), q(node_valid), counters.data_ptr(), costs.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
+            q(wri), q(node_valid), counters.data_ptr(), costs.data_ptr(), self._stream())
         self._L.check(rc, "gtsfm_rotation_averaging_f64")
         c = counters.cpu().numpy()
         return {"wRi": wri, "node_valid": node_valid, "counters": c, "costs": costs.cpu().numpy(), "status": [STATUS_NAMES[int(s)] for s in c[:, 0]]}
 
     def upload(self, pair_images, rotation, weight, pair_enable=None, problem_row_off=None):
         """Host arrays -> the five device tensors ``average`` takes, in its order (None stays None)."""
-        torch = self._torch
-
-        def up(a, dt, shape):
-            return None if a is None else torch.from_numpy(np.ascontiguousarray(np.asarray(a, dtype=dt).reshape(shape))).to(self.device)
-
+        up = self._up
         return (up(pair_images, np.int32, (-1, 2)), up(rotation, np.float64, (-1, 9)), up(weight, np.float64, (-1,)), up(pair_enable, np.uint8, (-1,)),
                 up(problem_row_off, np.int64, (-1,)))

@@ -8,17 +8,22 @@ from typing import Dict, Iterable, List, Optional, Sequence, Tuple
 
 import numpy as np
 
-from gtsfm_amd.runtime.engine_base import EngineBase
+from gtsfm_amd.runtime.engine_base import EngineBase, named
 
 COUNT_FIELDS = ("tracks", "measurements", "discarded", "components", "rounds")
 
 
+def edge_selection(pairs: Sequence[Tuple[int, int]], edges: Iterable[Tuple[int, int]]) -> np.ndarray:
+    """[len(pairs)] uint8: 1 for a pair that ``edges`` lists. The one place a scene's stages look their ``edges=`` argument up."""
+    wanted = {(int(a), int(b)) for a, b in edges}
+    return np.fromiter((p in wanted for p in pairs), dtype=np.uint8, count=len(pairs))
+
+
 class TracksEngine(EngineBase):
     def _workspace(self, num_nodes: int, total: int):
-        need = int(self._lib.gtsfm_tracks_workspace_bytes(num_nodes, total))
-        if need == 0 and num_nodes > 0:
-            raise ValueError(f"gtsfm_tracks_workspace_bytes refuses {num_nodes} nodes / {total} match rows")
-        return self._grow(need)
+        if num_nodes == 0:  # a scene without nodes is no refusal
+            return self._grow(int(self._lib.gtsfm_tracks_workspace_bytes(0, total)))
+        return self._sized_workspace("gtsfm_tracks_workspace_bytes", num_nodes, total)
 
     def tracks_from_device(self, match_idx, match_off, pair_images, node_off, match_count=None, mask=None, pair_enable=None, kp_xy=None,
                            num_nodes: Optional[int] = None) -> Dict[str, object]:
@@ -37,11 +42,9 @@ class TracksEngine(EngineBase):
         total = int(match_idx.numel()) // 2
         if num_nodes is None:
             num_nodes = int(noff[-1].item()) if num_images >= 0 and noff.numel() else 0
-        for name, t, dt, n in (("match_idx", match_idx, torch.int32, 2 * total), ("match_count", match_count, torch.int32, num_pairs),
-                               ("mask", mask, torch.uint8, total), ("pair_enable", pair_enable, torch.uint8, num_pairs),
-                               ("kp_xy", kp_xy, torch.float32, 2 * num_nodes)):
-            if t is not None and not (t.is_cuda and t.dtype == dt and t.is_contiguous() and t.numel() == n):
-                raise TypeError(f"{name} must be a contiguous {dt} device tensor of {n} entries")
+        self._check_tensors((("match_idx", match_idx, torch.int32, 2 * total), ("match_count", match_count, torch.int32, num_pairs), ("mask", mask, torch.uint8, total),
+                             ("pair_enable", pair_enable, torch.uint8, num_pairs), ("kp_xy", kp_xy, torch.float32, 2 * num_nodes)),
+                            optional=("match_idx", "match_count", "mask", "pair_enable", "kp_xy"))
         cap = min(num_nodes, 2 * total)
         track_off = torch.empty(cap + 1, dtype=torch.int64, device=self.device)
         image = torch.empty(cap, dtype=torch.int32, device=self.device)
@@ -49,16 +52,14 @@ class TracksEngine(EngineBase):
         uv = torch.empty((cap, 2), dtype=torch.float32, device=self.device) if kp_xy is not None else None
         counts = torch.empty(8, dtype=torch.int32, device=self.device)
         ws = self._workspace(num_nodes, total) if num_pairs and total else None
-        ptr = self._L.ptr
+        ptr = self._ptr
         rc = self._lib.gtsfm_tracks_from_matches(
-            ptr(match_idx) if total else None, moff.data_ptr(), ptr(match_count), ptr(mask) if total else None, ptr(pair_enable),
-            pimg.data_ptr() if num_pairs else None, num_pairs, total, noff.data_ptr(), num_images, ptr(kp_xy), ptr(ws), 0 if ws is None else ws.numel(),
-            track_off.data_ptr(), ptr(image) if cap else None, ptr(kp) if cap else None, ptr(uv) if cap else None, counts.data_ptr(),
-            torch.cuda.current_stream(self.device).cuda_stream)
+            ptr(match_idx), moff.data_ptr(), ptr(match_count), ptr(mask), ptr(pair_enable), ptr(pimg), num_pairs, total, noff.data_ptr(), num_images, ptr(kp_xy), ptr(ws),
+            0 if ws is None else ws.numel(), track_off.data_ptr(), ptr(image), ptr(kp), ptr(uv), counts.data_ptr(), self._stream())
         self._L.check(rc, "gtsfm_tracks_from_matches")
         c = counts.cpu().numpy()
         t, s = int(c[0]), int(c[1])
-        out = {"track_off": track_off[: t + 1], "image": image[:s], "kp": kp[:s], "counts": {k: int(c[i]) for i, k in enumerate(COUNT_FIELDS)}}
+        out = {"track_off": track_off[: t + 1], "image": image[:s], "kp": kp[:s], "counts": named(c, COUNT_FIELDS)}
         if uv is not None:
             out["uv"] = uv[:s]
         return out
@@ -110,8 +111,6 @@ class TracksEngine(EngineBase):
             }
         enable = st["enable"]
         if edges is not None:
-            wanted = {(int(a), int(b)) for a, b in edges}
-            sel = np.fromiter((p in wanted for p in st["pairs"]), dtype=np.uint8, count=len(st["pairs"]))
-            enable = enable & torch.from_numpy(sel).to(self.device)
+            enable = enable & torch.from_numpy(edge_selection(st["pairs"], edges)).to(self.device)
         return self.tracks_from_device(st["match_idx"], st["match_off"], st["pair_images"], st["node_off"], match_count=st["match_count"], mask=st["mask"],
                                        pair_enable=enable, kp_xy=kp_xy, num_nodes=int(num_images) * int(cap))

@@ -9,7 +9,7 @@ from typing import Dict, Optional
 
 import numpy as np
 
-from gtsfm_amd.runtime.engine_base import EngineBase
+from gtsfm_amd.runtime.engine_base import EngineBase, named
 
 COUNT_FIELDS = ("pair_edges", "measurement_edges", "nodes", "inlier_pairs", "inlier_measurements", "inlier_cameras")
 OUTLIER_WEIGHT_THRESHOLD = 0.125
@@ -25,12 +25,6 @@ def lds_node_limit(value: Optional[int] = None) -> int:
 
 
 class TranslationInliersEngine(EngineBase):
-    def _workspace(self, *sizes):
-        need = int(self._lib.gtsfm_translation_inliers_workspace_bytes(*sizes))
-        if need == 0:
-            raise ValueError(f"gtsfm_translation_inliers_workspace_bytes refuses {sizes}")
-        return self._grow(need)
-
     def inliers(self, pair_images, pair_direction, pair_enable, rotation, rotation_valid, intrinsics, track_off, image, uv, track_enable, meas_enable, directions, *,
                 threshold: float = OUTLIER_WEIGHT_THRESHOLD, world=None, node_capacity: Optional[int] = None, lds_nodes: Optional[int] = None,
                 want_position: bool = False) -> Dict[str, object]:
@@ -54,16 +48,12 @@ class TranslationInliersEngine(EngineBase):
         else:
             spec += [("pair_direction", pair_direction, torch.float64, 3 * e), ("rotation", rotation, torch.float64, 9 * n), ("intrinsics", intrinsics, torch.float64, 4 * n),
                      ("uv", uv, torch.float32, 2 * s)]
-        for name, x, dt, count in spec:
-            if x is None and name in ("pair_enable", "meas_enable"):
-                continue
-            if not (isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == dt and x.is_contiguous() and x.numel() == count):
-                raise TypeError(f"{name} must be a contiguous {dt} device tensor of {count} entries")
+        self._check_tensors(spec, optional=("pair_enable", "meas_enable"))
         if t < 0 or (s > 0 and t == 0):
             raise ValueError("track_off must be [T + 1] with T > 0 when there are measurements")
         limit = lds_node_limit(lds_nodes)
         cap = n + t if node_capacity is None else min(int(node_capacity), n + t)
-        ws = self._workspace(e, s, n, t, d, cap, limit)
+        ws = self._sized_workspace("gtsfm_translation_inliers_workspace_bytes", e, s, n, t, d, cap, limit)
         world_pair = world[0].clone() if given else torch.empty((e, 3), dtype=torch.float64, device=dev)
         world_meas = world[1].clone() if given else torch.empty((s, 3), dtype=torch.float64, device=dev)
         pair_weight, meas_weight = torch.empty(e, dtype=torch.float64, device=dev), torch.empty(s, dtype=torch.float64, device=dev)
@@ -71,16 +61,15 @@ class TranslationInliersEngine(EngineBase):
         camera_inlier = torch.empty(n, dtype=torch.uint8, device=dev)
         position = torch.empty((d, n + t), dtype=torch.int32, device=dev) if want_position else None
         counts = torch.empty(8, dtype=torch.int32, device=dev)
-        ptr = self._L.ptr
-        p = lambda x: ptr(x) if x is not None and x.numel() else None  # noqa: E731
+        p = self._ptr
         rc = self._lib.gtsfm_translation_inliers_f64(
-            p(pair_images), p(pair_direction), p(pair_enable), e, p(rotation), p(rotation_valid), p(intrinsics), n, ptr(track_off), p(image), p(uv), p(track_enable),
+            p(pair_images), p(pair_direction), p(pair_enable), e, p(rotation), p(rotation_valid), p(intrinsics), n, track_off.data_ptr(), p(image), p(uv), p(track_enable),
             p(meas_enable), t, s, p(directions), d, float(threshold), 1 if given else 0, cap, limit, ws.data_ptr(), ws.numel(), p(world_pair), p(world_meas), p(pair_weight),
-            p(meas_weight), p(pair_inlier), p(meas_inlier), p(camera_inlier), p(position), counts.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
+            p(meas_weight), p(pair_inlier), p(meas_inlier), p(camera_inlier), p(position), counts.data_ptr(), self._stream())
         self._L.check(rc, "gtsfm_translation_inliers_f64")
         c = counts.cpu().numpy()
         out = {"world_pair": world_pair, "world_meas": world_meas, "pair_weight": pair_weight, "meas_weight": meas_weight, "pair_inlier": pair_inlier,
-               "meas_inlier": meas_inlier, "camera_inlier": camera_inlier, "counts": {k: int(c[i]) for i, k in enumerate(COUNT_FIELDS)}, "counts_raw": c,
+               "meas_inlier": meas_inlier, "camera_inlier": camera_inlier, "counts": named(c, COUNT_FIELDS), "counts_raw": c,
                "tier": "lds" if int(c[2]) <= limit else "workspace"}
         if want_position:
             out["position"] = position
@@ -88,16 +77,11 @@ class TranslationInliersEngine(EngineBase):
 
     def upload(self, pair_images, pair_direction, pair_enable, rotation, rotation_valid, intrinsics, track_off, image, uv, track_enable, meas_enable, directions):
         """Host arrays -> the twelve device tensors ``inliers`` takes, in its order (None stays None)."""
-        torch = self._torch
-
-        def up(a, dt, shape):
-            return None if a is None else torch.from_numpy(np.ascontiguousarray(np.asarray(a, dtype=dt).reshape(shape))).to(self.device)
-
+        up = self._up
         return (up(pair_images, np.int32, (-1, 2)), up(pair_direction, np.float64, (-1, 3)), up(pair_enable, np.uint8, (-1,)), up(rotation, np.float64, (-1, 9)),
                 up(rotation_valid, np.uint8, (-1,)), up(intrinsics, np.float64, (-1, 4)), up(track_off, np.int64, (-1,)), up(image, np.int32, (-1,)),
                 up(uv, np.float32, (-1, 2)), up(track_enable, np.uint8, (-1,)), up(meas_enable, np.uint8, (-1,)), up(directions, np.float64, (-1, 3)))
 
     def upload_world(self, world_pair, world_meas):
         """Host world directions [E, 3] and [S, 3] -> the ``world=`` pair of ``inliers``."""
-        torch = self._torch
-        return tuple(torch.from_numpy(np.ascontiguousarray(np.asarray(a, dtype=np.float64).reshape(-1, 3))).to(self.device) for a in (world_pair, world_meas))
+        return self._up(world_pair, np.float64, (-1, 3)), self._up(world_meas, np.float64, (-1, 3))

@@ -9,7 +9,7 @@ from typing import Dict
 
 import numpy as np
 
-from gtsfm_amd.runtime.engine_base import EngineBase
+from gtsfm_amd.runtime.engine_base import EngineBase, merge_options
 
 COUNTER_FIELDS = ("status", "outer_iterations", "accepted_steps", "hessian_applications", "init_cg_steps", "component_size", "anchor", "valid_rows")
 COST_FIELDS = ("init_cost", "final_cost", "gradient_inf_norm", "trust_radius")
@@ -22,12 +22,6 @@ DEFAULTS = dict(scale_factor=1.0, sigma=0.01, huber_k=1.3, init_tol=1e-10, init_
 
 
 class TranslationRecoveryEngine(EngineBase):
-    def _workspace(self, *sizes):
-        need = int(self._lib.gtsfm_translation_recovery_workspace_bytes(*sizes))
-        if need == 0:
-            raise ValueError(f"gtsfm_translation_recovery_workspace_bytes refuses {sizes}")
-        return self._grow(need)
-
     def recover(self, pair_images, world_pair, pair_enable, track_off, image, world_meas, meas_enable, *, num_images: int, anchor: int = -1, problem_row_off=None,
                 **options) -> Dict[str, object]:
         """Device tensors as in include/gtsfm_amd.h: ``pair_images`` [E, 2] int32 = (i1, i2), ``world_pair`` [E, 3] float64 = w_i2Ui1, ``pair_enable``
@@ -38,10 +32,7 @@ class TranslationRecoveryEngine(EngineBase):
         int32, ``costs`` [P, 4] float64 and ``status`` (a list of names). The inputs are not changed."""
         torch = self._torch
         dev = self.device
-        unknown = set(options) - set(DEFAULTS)
-        if unknown:
-            raise TypeError(f"unknown options {sorted(unknown)}")
-        o = dict(DEFAULTS, **options)
+        o = merge_options(DEFAULTS, options)
         e, n = int(pair_images.shape[0]) if pair_images is not None else 0, int(num_images)
         t = 0 if track_off is None else int(track_off.shape[0]) - 1
         s = 0 if image is None else int(image.shape[0])
@@ -55,36 +46,28 @@ class TranslationRecoveryEngine(EngineBase):
                 raise ValueError("problem_row_off must be [P + 1, 2] with P >= 1")
             t_max = int(min(max(int(np.diff(off[:, 1]).max()), 0), t))
             off_dev = torch.from_numpy(off).to(dev)
-        for name, x, dt, count in (("pair_images", pair_images, torch.int32, 2 * e), ("world_pair", world_pair, torch.float64, 3 * e), ("pair_enable", pair_enable, torch.uint8, e),
-                                   ("track_off", track_off, torch.int64, t + 1), ("image", image, torch.int32, s), ("world_meas", world_meas, torch.float64, 3 * s),
-                                   ("meas_enable", meas_enable, torch.uint8, s)):
-            if x is None and (name in ("pair_enable", "meas_enable", "track_off") or count == 0):
-                continue
-            if not (isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == dt and x.is_contiguous() and x.numel() == count):
-                raise TypeError(f"{name} must be a contiguous {dt} device tensor of {count} entries")
+        spec = (("pair_images", pair_images, torch.int32, 2 * e), ("world_pair", world_pair, torch.float64, 3 * e), ("pair_enable", pair_enable, torch.uint8, e),
+                ("track_off", track_off, torch.int64, t + 1), ("image", image, torch.int32, s), ("world_meas", world_meas, torch.float64, 3 * s),
+                ("meas_enable", meas_enable, torch.uint8, s))
+        self._check_tensors(spec, optional={"pair_enable", "meas_enable", "track_off"} | {row[0] for row in spec if row[3] == 0})  # or nothing to hold
         m = n + t_max
-        ws = self._workspace(e, s, n, t, t_max, p)
+        ws = self._sized_workspace("gtsfm_translation_recovery_workspace_bytes", e, s, n, t, t_max, p)
         translation = torch.empty((p, m, 3), dtype=torch.float64, device=dev)
         node_valid = torch.empty((p, m), dtype=torch.uint8, device=dev)
         counters = torch.empty((p, 8), dtype=torch.int32, device=dev)
         costs = torch.empty((p, 4), dtype=torch.float64, device=dev)
-        ptr = self._L.ptr
-        q = lambda x: ptr(x) if x is not None and x.numel() else None  # noqa: E731
+        q = self._ptr
         rc = self._lib.gtsfm_translation_recovery_f64(
-            q(pair_images), q(world_pair), q(pair_enable), e, ptr(track_off) if t > 0 else None, q(image), q(world_meas), q(meas_enable), t, s, n, q(off_dev), p, t_max, int(anchor),
+            q(pair_images), q(world_pair), q(pair_enable), e, q(track_off) if t > 0 else None, q(image), q(world_meas), q(meas_enable), t, s, n, q(off_dev), p, t_max, int(anchor),
             float(o["scale_factor"]), float(o["sigma"]), float(o["huber_k"]), float(o["init_tol"]), int(o["init_max_iterations"]), float(o["delta0"]), float(o["kappa_cg"]),
             float(o["gradient_tol"]), float(o["rel_tol"]), float(o["abs_tol"]), int(o["max_outer"]), int(o["max_inner"]), ws.data_ptr(), ws.numel(), q(translation),
-            q(node_valid), counters.data_ptr(), costs.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
+            q(node_valid), counters.data_ptr(), costs.data_ptr(), self._stream())
         self._L.check(rc, "gtsfm_translation_recovery_f64")
         c = counters.cpu().numpy()
         return {"translation": translation, "node_valid": node_valid, "counters": c, "costs": costs.cpu().numpy(), "status": [STATUS_NAMES[int(k)] for k in c[:, 0]]}
 
     def upload(self, pair_images, world_pair, pair_enable=None, track_off=None, image=None, world_meas=None, meas_enable=None):
         """Host arrays -> the seven device tensors ``recover`` takes, in its order (None stays None)."""
-        torch = self._torch
-
-        def up(a, dt, shape):
-            return None if a is None else torch.from_numpy(np.ascontiguousarray(np.asarray(a, dtype=dt).reshape(shape))).to(self.device)
-
+        up = self._up
         return (up(pair_images, np.int32, (-1, 2)), up(world_pair, np.float64, (-1, 3)), up(pair_enable, np.uint8, (-1,)), up(track_off, np.int64, (-1,)),
                 up(image, np.int32, (-1,)), up(world_meas, np.float64, (-1, 3)), up(meas_enable, np.uint8, (-1,)))

@@ -42,12 +42,6 @@ def pack_cameras(cameras: Dict[int, object], num_images: Optional[int] = None) -
 
 
 class TriangulationEngine(EngineBase):
-    def _workspace(self, num_tracks: int, total: int, max_hyp: int):
-        need = int(self._lib.gtsfm_triangulate_workspace_bytes(num_tracks, total, max_hyp))
-        if need == 0:
-            raise ValueError(f"gtsfm_triangulate_workspace_bytes refuses {num_tracks} tracks / {total} measurements / {max_hyp} hypotheses")
-        return self._grow(need)
-
     def triangulate(self, track_off, image, uv, cameras, mode="NO_RANSAC", reproj_error_threshold: float = float("inf"),
                     min_triangulation_angle_deg: float = 0.0, num_hypotheses: int = 2749, seed: int = 0) -> Dict[str, object]:
         """``track_off`` [T + 1] int64, ``image`` [S] int32, ``uv`` [S, 2] float32: device tensors (used where they lie) or host arrays;
@@ -70,12 +64,12 @@ class TriangulationEngine(EngineBase):
                "stats": torch.zeros((num_tracks, 4), dtype=torch.int32, device=self.device)}
         if num_tracks == 0:
             return out
-        ws = self._workspace(num_tracks, total, max_hyp)
-        ptr = self._L.ptr
+        ws = self._sized_workspace("gtsfm_triangulate_workspace_bytes", num_tracks, total, max_hyp)
+        ptr = self._ptr
         rc = self._lib.gtsfm_triangulate_tracks_f64(
-            off.data_ptr(), ptr(img) if total else None, ptr(xy) if total else None, num_tracks, total, ptr(cams) if cams.numel() else None, int(cams.shape[0]),
+            off.data_ptr(), ptr(img), ptr(xy), num_tracks, total, ptr(cams), int(cams.shape[0]),
             mode_id, float(reproj_error_threshold), float(min_triangulation_angle_deg), max_hyp, int(seed) & ((1 << 64) - 1), ws.data_ptr(), ws.numel(),
-            out["point"].data_ptr(), out["avg_error"].data_ptr(), out["exit_code"].data_ptr(), ptr(out["inlier_mask"]) if total else None,
-            out["stats"].data_ptr(), torch.cuda.current_stream(self.device).cuda_stream)
+            out["point"].data_ptr(), out["avg_error"].data_ptr(), out["exit_code"].data_ptr(), ptr(out["inlier_mask"]), out["stats"].data_ptr(),
+            self._stream())
         self._L.check(rc, "gtsfm_triangulate_tracks_f64")
         return out

@@ -32,12 +32,6 @@ class TwoViewBAOptions:
 
 
 class TwoViewBAEngine(EngineBase):
-    def _workspace(self, num_pairs: int, total: int):
-        need = int(self._lib.gtsfm_two_view_ba_workspace_bytes(num_pairs, total))
-        if need == 0:
-            raise ValueError(f"gtsfm_two_view_ba_workspace_bytes refuses {num_pairs} pairs / {total} matches")
-        return self._grow(need)
-
     def run(self, launch: Dict[str, object], options: Optional[TwoViewBAOptions] = None) -> Dict[str, object]:
         """``launch``: one verifier launch's arrays, device tensors (used where they lie) or host arrays -- ``kp_xy`` [*, 2] float32,
         ``kp_off1`` / ``kp_off2`` [P] int64, ``match_idx`` [M, 2] int32, ``match_off`` [P + 1] int64, ``match_count`` [P] int32 or None,
@@ -69,15 +63,14 @@ class TwoViewBAEngine(EngineBase):
                "cost": torch.full((num_pairs, 2), nan, dtype=torch.float64, device=self.device)}
         stats = torch.zeros((num_pairs, 8), dtype=torch.int32, device=self.device)
         if num_pairs:
-            ws = self._workspace(num_pairs, total)
-            ptr = self._L.ptr
+            ws = self._sized_workspace("gtsfm_two_view_ba_workspace_bytes", num_pairs, total)
+            ptr = self._ptr
             rc = self._lib.gtsfm_two_view_ba_f64(
-                ptr(kp) if total else None, off1.data_ptr(), off2.data_ptr(), ptr(idx) if total else None, moff.data_ptr(), ptr(count), total,
-                ptr(mask) if total else None, intr.data_ptr(), rot.data_ptr(), trans.data_ptr(), num_pairs, int(opt.max_iterations),
-                float(opt.reproj_error_threshold), float(opt.huber_k), float(opt.measurement_sigma), float(opt.pose_prior_sigma), float(opt.point_prior_sigma),
-                int(opt.min_verified), int(bool(opt.allow_indeterminate)), float(opt.triangulation_threshold), float(opt.triangulation_min_angle_deg),
-                ws.data_ptr(), ws.numel(), out["rotation"].data_ptr(), out["translation"].data_ptr(), ptr(out["valid_mask"]) if total else None,
-                ptr(out["point"]) if total else None, out["cost"].data_ptr(), stats.data_ptr(), torch.cuda.current_stream(self.device).cuda_stream)
+                ptr(kp) if total else None, off1.data_ptr(), off2.data_ptr(), ptr(idx), moff.data_ptr(), ptr(count), total, ptr(mask), intr.data_ptr(), rot.data_ptr(),
+                trans.data_ptr(), num_pairs, int(opt.max_iterations), float(opt.reproj_error_threshold), float(opt.huber_k), float(opt.measurement_sigma),
+                float(opt.pose_prior_sigma), float(opt.point_prior_sigma), int(opt.min_verified), int(bool(opt.allow_indeterminate)), float(opt.triangulation_threshold),
+                float(opt.triangulation_min_angle_deg), ws.data_ptr(), ws.numel(), out["rotation"].data_ptr(), out["translation"].data_ptr(), ptr(out["valid_mask"]),
+                ptr(out["point"]), out["cost"].data_ptr(), stats.data_ptr(), self._stream())
             self._L.check(rc, "gtsfm_two_view_ba_f64")
         out["stats"] = stats.cpu().numpy()
         return out

@@ -68,11 +68,10 @@ class VerifierEngine(EngineBase):
         if num_pairs == 0:
             return out
         ws = self._workspace(total)
-        head = (kp_xy.data_ptr(), off1.data_ptr(), off2.data_ptr(), match_idx.data_ptr() if total else None, moff.data_ptr(),
-                match_count.data_ptr() if match_count is not None else None, total, intr.data_ptr(), seeds_dev.data_ptr(), float(threshold_px),
-                num_pairs, ws.data_ptr(), ws.numel())
-        tail = (out["E"].data_ptr(), out["R"].data_ptr(), out["t"].data_ptr(), out["mask"].data_ptr() if total else None,
-                out["stats"].data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
+        ptr = self._ptr
+        head = (kp_xy.data_ptr(), off1.data_ptr(), off2.data_ptr(), ptr(match_idx), moff.data_ptr(), ptr(match_count), total, intr.data_ptr(), seeds_dev.data_ptr(),
+                float(threshold_px), num_pairs, ws.data_ptr(), ws.numel())
+        tail = (out["E"].data_ptr(), out["R"].data_ptr(), out["t"].data_ptr(), ptr(out["mask"]), out["stats"].data_ptr(), self._stream())
         if use_intrinsics:
             _lib.check(self._lib.gtsfm_verify_essential_f64(*head, *tail), "gtsfm_verify_essential_f64")
         else:
@@ -91,8 +90,7 @@ class VerifierEngine(EngineBase):
             rows_dev, n0_dev, off_dev = self._dev(row_off, torch.int64), self._dev(n0, torch.int32), self._dev(match_off, torch.int64)  # keep alive
             _lib.check(
                 self._lib.gtsfm_verify_compact_matches(
-                    matches.data_ptr(), rows_dev.data_ptr(), n0_dev.data_ptr(), off_dev.data_ptr(), num_pairs, idx.data_ptr(), count.data_ptr(),
-                    torch.cuda.current_stream(self.device).cuda_stream,
+                    matches.data_ptr(), rows_dev.data_ptr(), n0_dev.data_ptr(), off_dev.data_ptr(), num_pairs, idx.data_ptr(), count.data_ptr(), self._stream()
                 ),
                 "gtsfm_verify_compact_matches",
             )

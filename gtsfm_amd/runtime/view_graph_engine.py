@@ -10,7 +10,7 @@ from typing import Dict
 
 import numpy as np
 
-from gtsfm_amd.runtime.engine_base import EngineBase
+from gtsfm_amd.runtime.engine_base import EngineBase, named
 
 MIN_EDGE_ERROR, MEDIAN_EDGE_ERROR = 0, 1
 CRITERIA = {"MIN_EDGE_ERROR": MIN_EDGE_ERROR, "MEDIAN_EDGE_ERROR": MEDIAN_EDGE_ERROR}
@@ -36,19 +36,11 @@ class ViewGraphEngine(EngineBase):
         super().__init__(device)
         self._triplet_capacity = 0
 
-    def _workspace(self, num_edges: int, num_images: int, triplets: int):
-        need = int(self._lib.gtsfm_view_graph_workspace_bytes(num_edges, num_images, triplets))
-        if need == 0:
-            raise ValueError(f"gtsfm_view_graph_workspace_bytes refuses {num_edges} edges / {num_images} images / {triplets} triplets")
-        return self._grow(need)
-
     def _check(self, pair_images, rotation, pair_enable, num_images):
         torch = self._torch
         num_edges = int(pair_images.shape[0]) if pair_images.dim() == 2 else -1
-        for name, t, dt, n in (("pair_images", pair_images, torch.int32, 2 * num_edges), ("rotation", rotation, torch.float64, 9 * num_edges),
-                               ("pair_enable", pair_enable, torch.uint8, num_edges)):
-            if t is not None and not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == dt and t.is_contiguous() and t.numel() == n):
-                raise TypeError(f"{name} must be a contiguous {dt} device tensor of {max(n, 0)} entries")
+        self._check_tensors((("pair_images", pair_images, torch.int32, 2 * num_edges), ("rotation", rotation, torch.float64, 9 * num_edges),
+                             ("pair_enable", pair_enable, torch.uint8, num_edges)), optional=("pair_images", "rotation", "pair_enable"))
         if num_edges < 0 or int(num_images) < 0:
             raise ValueError(f"pair_images must be [E, 2] and num_images >= 0 (got {tuple(pair_images.shape)}, {num_images})")
         return num_edges
@@ -68,15 +60,14 @@ class ViewGraphEngine(EngineBase):
         counts = torch.empty(8, dtype=torch.int32, device=self.device)
         capacity = max(self._triplet_capacity, 8 * num_edges)
         found = C.c_longlong(-1)
-        ptr = self._L.ptr
+        ptr = self._ptr
         for attempt in range(2):
-            ws = self._workspace(num_edges, int(num_images), capacity)
+            ws = self._sized_workspace("gtsfm_view_graph_workspace_bytes", num_edges, int(num_images), capacity)
             trip = torch.empty((capacity, 3), dtype=torch.int32, device=self.device) if want_triplets else None
             cyc = torch.empty(capacity, dtype=torch.float64, device=self.device) if want_triplets else None
             rc = self._lib.gtsfm_view_graph_cycle_filter_f64(
-                ptr(pair_images) if num_edges else None, ptr(rotation) if num_edges else None, ptr(pair_enable) if num_edges else None, num_edges, int(num_images), code,
-                float(error_threshold), capacity, ws.data_ptr(), ws.numel(), ptr(num) if num_edges else None, ptr(agg) if num_edges else None,
-                ptr(keep) if num_edges else None, counts.data_ptr(), ptr(trip), ptr(cyc), C.byref(found), torch.cuda.current_stream(self.device).cuda_stream)
+                ptr(pair_images), ptr(rotation), ptr(pair_enable), num_edges, int(num_images), code, float(error_threshold), capacity, ws.data_ptr(), ws.numel(), ptr(num),
+                ptr(agg), ptr(keep), counts.data_ptr(), ptr(trip), ptr(cyc), C.byref(found), self._stream())
             if rc == WORKSPACE_ERROR and found.value > capacity and attempt == 0:
                 capacity = int(found.value)  # the call counted them before it refused
                 continue
@@ -84,7 +75,7 @@ class ViewGraphEngine(EngineBase):
         self._L.check(rc, "gtsfm_view_graph_cycle_filter_f64")
         self._triplet_capacity = capacity
         c = counts.cpu().numpy()
-        out = {"num_triplets": num, "aggregate_error": agg, "keep": keep, "counts": {k: int(c[i]) for i, k in enumerate(FILTER_COUNT_FIELDS)}}
+        out = {"num_triplets": num, "aggregate_error": agg, "keep": keep, "counts": named(c, FILTER_COUNT_FIELDS)}
         if want_triplets:
             out["triplets"], out["cycle_error"] = trip[: int(c[2])], cyc[: int(c[2])]
         return out
@@ -96,19 +87,13 @@ class ViewGraphEngine(EngineBase):
         node_mask = torch.empty(int(num_images), dtype=torch.uint8, device=self.device)
         pair_keep = torch.empty(num_edges, dtype=torch.uint8, device=self.device)
         counts = torch.empty(8, dtype=torch.int32, device=self.device)
-        ws = self._workspace(num_edges, int(num_images), 0)
-        ptr = self._L.ptr
-        rc = self._lib.gtsfm_largest_component(ptr(pair_images) if num_edges else None, ptr(pair_enable) if num_edges else None, num_edges, int(num_images), ws.data_ptr(),
-                                               ws.numel(), ptr(node_mask) if num_images else None, ptr(pair_keep) if num_edges else None, counts.data_ptr(),
-                                               torch.cuda.current_stream(self.device).cuda_stream)
+        ws = self._sized_workspace("gtsfm_view_graph_workspace_bytes", num_edges, int(num_images), 0)
+        ptr = self._ptr
+        rc = self._lib.gtsfm_largest_component(ptr(pair_images), ptr(pair_enable), num_edges, int(num_images), ws.data_ptr(), ws.numel(), ptr(node_mask), ptr(pair_keep),
+                                               counts.data_ptr(), self._stream())
         self._L.check(rc, "gtsfm_largest_component")
-        c = counts.cpu().numpy()
-        return {"node_mask": node_mask, "pair_keep": pair_keep, "counts": {k: int(c[i]) for i, k in enumerate(COMPONENT_COUNT_FIELDS)}}
+        return {"node_mask": node_mask, "pair_keep": pair_keep, "counts": named(counts.cpu().numpy(), COMPONENT_COUNT_FIELDS)}
 
     def upload(self, pair_images, rotation=None, pair_enable=None):
         """Host arrays -> the device tensors the two methods take."""
-        torch = self._torch
-        pimg = torch.from_numpy(np.ascontiguousarray(np.asarray(pair_images).reshape(-1, 2), dtype=np.int32)).to(self.device)
-        rot = None if rotation is None else torch.from_numpy(np.ascontiguousarray(np.asarray(rotation, dtype=np.float64).reshape(-1, 9))).to(self.device)
-        en = None if pair_enable is None else torch.from_numpy(np.ascontiguousarray(pair_enable, dtype=np.uint8)).to(self.device)
-        return pimg, rot, en
+        return self._up(pair_images, np.int32, (-1, 2)), self._up(rotation, np.float64, (-1, 9)), self._up(pair_enable, np.uint8, (-1,))

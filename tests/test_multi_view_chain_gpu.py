@@ -51,8 +51,10 @@ def planted_generator(sc, device):
     return PlantedGenerator(TwoWayMatcher(), SIFTDetectorDescriptor(max_keypoints=M.CAP))
 
 
-def run_chain(sc, device, threshold, launch_pairs=None):
-    """The whole chain on the device; ``launch_pairs``: pairs per verifier launch (None: the generator's own limit, one launch here)."""
+def run_chain(sc, device, threshold, launch_pairs=None, other_order_first=False):
+    """The whole chain on the device; ``launch_pairs``: pairs per verifier launch (None: the generator's own limit, one launch here);
+    ``other_order_first``: on the scene ``two_view`` returned, ``tracks`` and then ``translation_inliers`` run once (over every edge) before
+    ``view_graph``, so the columns of the scene's edge table are built in another order than the chain's."""
     from gtsfm_amd.bundle.two_view_ba import TwoViewOptions
     from gtsfm_amd.common.calibration import PinholeCamera, PinholeIntrinsics
     from gtsfm_amd.data_association.point3d_initializer import TriangulationOptions, TriangulationSamplingMode
@@ -69,11 +71,17 @@ def run_chain(sc, device, threshold, launch_pairs=None):
         scene = gen.generate_verified_scene(None, [None] * M.NUM_IMAGES, sc["edges"], cals, Ransac(True, M.VERIFY_THRESHOLD_PX))
     before = [{k: host(v).copy() for k, v in ver.items() if k in LAUNCH_KEYS} for ver in scene.launches] + [{"xy": host(scene.feats["xy"]).copy()}]
     new = scene.two_view(TwoViewOptions(min_num_inliers_est_model=M.MIN_INLIERS, min_inlier_ratio_est_model=M.MIN_RATIO), cals)
+    rotations = [sc["wRi"][i] for i in range(M.NUM_IMAGES)]
+    if other_order_first:
+        new.tracks()
+        early = ShortAveraging()
+        early._outlier_weight_threshold = threshold
+        new.translation_inliers(rotations, cals, averaging=early)
     vg = new.view_graph()
     averaging = ShortAveraging()
     assert M.NUM_DIRECTIONS == 64
     averaging._outlier_weight_threshold = threshold
-    ti = new.translation_inliers([sc["wRi"][i] for i in range(M.NUM_IMAGES)], cals, edges=vg.edges, averaging=averaging)
+    ti = new.translation_inliers(rotations, cals, edges=vg.edges, averaging=averaging)
     tracks = new.tracks(edges=ti.edges)
     options = TriangulationOptions(mode=TriangulationSamplingMode.NO_RANSAC, reproj_error_threshold=M.TRIANGULATION_THRESHOLD_PX)
     tri = new.triangulate(cameras, options, edges=ti.edges)
@@ -374,3 +382,11 @@ def test_the_scene_is_untouched_and_the_chain_repeats_and_does_not_depend_on_the
     assert len(merged["scene"].launches) == 1 and len(device_chain["scene"].launches) == 2
     one = chain_bytes(merged)
     assert [k for k in first if first[k] != one[k]] == []
+
+
+def test_the_chain_does_not_depend_on_the_order_in_which_the_stages_first_ran(device_chain, restated, gpu_device):
+    """``tracks`` first and ``translation_inliers`` before ``view_graph`` on one scene: each stage builds what it needs of the scene's edge
+    table on first use, so the order of the first calls must not show in any result."""
+    first = chain_bytes(device_chain)
+    other = chain_bytes(run_chain(restated["scene"], gpu_device, restated["threshold"], launch_pairs=M.LAUNCH_PAIRS, other_order_first=True))
+    assert [k for k in first if first[k] != other[k]] == []
