@@ -3,6 +3,7 @@
 #pragma once
 
 #include <hip/hip_runtime.h>
+#include <stdarg.h>
 #include <stdint.h>
 #include <stdio.h>
 
@@ -52,6 +53,21 @@ struct WorkspaceCarver {
     }
     void* take(size_t bytes) { return (void*)((uintptr_t)base + offset(bytes)); }
 };
+
+// The two checks every call makes of its workspace: GTSFM_OK, or the status with the error set. `holds` is the caller's verdict, bytes >=
+// needed unless it knows of another reason; `sizes` and its arguments say what the bytes are needed for.
+__attribute__((format(printf, 6, 7))) static inline int gtsfm_check_workspace(const char* me, const void* base, bool holds, size_t bytes, size_t needed, const char* sizes,
+                                                                              ...) {
+    GTSFM_CHECK_ARG(base && ((uintptr_t)base & 255) == 0, "%s: the workspace must be aligned to 256 bytes", me);
+    if (holds) return GTSFM_OK;
+    char what[192];
+    va_list args;
+    va_start(args, sizes);
+    vsnprintf(what, sizeof(what), sizes, args);
+    va_end(args);
+    gtsfm_set_error("%s: workspace of %zu bytes, %zu needed for %s", me, bytes, needed, what);
+    return GTSFM_ERR_WORKSPACE;
+}
 
 // Wave-wide reductions over all 64 lanes (result valid in every lane).
 __device__ __forceinline__ float wave_sum(float v) {

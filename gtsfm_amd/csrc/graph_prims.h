@@ -1,7 +1,7 @@
 // Graph building blocks shared by the tracks, the view graph and 1DSfM (rotation averaging takes the atomic shim only): host/device
 // atomics, the workgroup scan and reduce, the single-workgroup prefix sum, the launch grid and the union-find rounds. Everything has
 // internal linkage: each translation unit keeps its own instantiation. The header compiles in both passes of hipcc, and the host builds
-// under tools/ call the GTSFM_HD functions on a CPU.
+// under tools/ call the GTSFM_HD functions on a CPU. stage_runner.h, built on this header, launches or walks the stages made of them.
 //
 // UNION-FIND LABELLING. label[] is a snapshot that a launch only reads, parent[] is the forest the same launch hooks into.
 //   init     : parent[v] = label[v] = v, marks / counters / flags cleared (the caller's kernel).
@@ -11,7 +11,7 @@
 //   compress : thread v chases parent[] from v to its root and stores label[v] = parent[v] = root. Only thread v stores parent[v] or
 //              label[v] in this launch; a chase that passes through w reads parent[w] before or after thread w's store, and both
 //              values lie on w's path to the same root.
-//   The host reads the round's 4-byte flag after the compress launch. A round that raised no flag found label[u] == label[v] for every
+//   The host reads the flag words up to the round's after the compress launch (one copy). A round that raised no flag found label[u] == label[v] for every
 //   active edge in data published by a launch boundary, so every component carries one label, and since parent[x] <= x that label is
 //   the component's smallest node. The host stops there, or fails at UF_MAX_ROUNDS without writing a result.
 //
@@ -154,24 +154,22 @@ GTSFM_HD void uf_compress(int* parent, int* label, long long v) {
     parent[v] = x;
 }
 
-enum UfOutcome { UF_FIXED_POINT, UF_BAD_INPUT, UF_NO_FIXED_POINT, UF_LAUNCH_FAILED, UF_READ_FAILED };
+enum UfOutcome { UF_FIXED_POINT, UF_BAD_INPUT, UF_NO_FIXED_POINT, UF_FAILED };
 
-// The rounds, on the host: hook(r) and compress() launch the caller's kernels on `stream` and return GTSFM_OK or, with the error set, another
-// status. *rounds: the rounds completed; the round that failed for UF_READ_FAILED. The caller words UF_BAD_INPUT, UF_NO_FIXED_POINT and
-// UF_READ_FAILED (hipGetLastError() holds the cause) with its own sizes.
-template <class Hook, class Compress>
-UfOutcome uf_run_rounds(const int* flags_dev, hipStream_t stream, Hook hook, Compress compress, int* rounds) {
+// The rounds, on the host: hook(r) and compress() run the caller's stages through `run` (a runner of stage_runner.h) and return GTSFM_OK
+// or, with the error set, another status; UF_FAILED is that, or a failed readback. *rounds: the rounds completed. The caller words
+// UF_BAD_INPUT and UF_NO_FIXED_POINT with its own sizes.
+template <class Runner, class Hook, class Compress>
+UfOutcome uf_run_rounds(Runner& run, const int* flags, Hook hook, Compress compress, int* rounds) {
     for (*rounds = 0;;) {
         if (*rounds == UF_MAX_ROUNDS) return UF_NO_FIXED_POINT;
-        if (hook(*rounds) != GTSFM_OK || compress() != GTSFM_OK) return UF_LAUNCH_FAILED;
-        int flag[2] = {0, 0};  // bad input, this round hooked
-        if (hipMemcpyAsync(&flag[0], flags_dev, sizeof(int), hipMemcpyDeviceToHost, stream) != hipSuccess ||
-            hipMemcpyAsync(&flag[1], flags_dev + 8 + *rounds, sizeof(int), hipMemcpyDeviceToHost, stream) != hipSuccess ||
-            hipStreamSynchronize(stream) != hipSuccess)
-            return UF_READ_FAILED;
+        if (hook(*rounds) != GTSFM_OK || compress() != GTSFM_OK) return UF_FAILED;
+        int flag[UF_FLAG_WORDS];  // word 0: bad input; word 8 + r: round r hooked
+        char what[16];
+        snprintf(what, sizeof(what), "round %d", *rounds);
+        if (run.fetch(flag, flags, (size_t)(8 + *rounds + 1), what) != GTSFM_OK) return UF_FAILED;
         if (flag[0]) return UF_BAD_INPUT;
-        ++*rounds;
-        if (!flag[1]) return UF_FIXED_POINT;
+        if (!flag[8 + (*rounds)++]) return UF_FIXED_POINT;
     }
 }
 

@@ -21,7 +21,7 @@
 //   write    : measurement moff[root] + rank <- (image, keypoint, xy); the root writes track_off; one thread the counts.
 
 #include "../../include/gtsfm_amd.h"
-#include "graph_prims.h"
+#include "stage_runner.h"
 
 #define TRK_THREADS 256
 #define TRK_SCAN_ITEMS 4                                // values per thread of a scan block
@@ -343,12 +343,9 @@ extern "C" int gtsfm_tracks_from_matches(const int32_t* match_idx_dev, const lon
         return GTSFM_OK;
     };
     int rounds = 0;
-    const UfOutcome labelled = uf_run_rounds(w.flags, stream, hook, compress, &rounds);
-    if (labelled == UF_LAUNCH_FAILED) return GTSFM_ERR_HIP;
-    if (labelled == UF_READ_FAILED) {
-        gtsfm_set_error("gtsfm_tracks_from_matches: round %d failed: %s", rounds, hipGetErrorString(hipGetLastError()));
-        return GTSFM_ERR_HIP;
-    }
+    DeviceRunner run{stream, "gtsfm_tracks_from_matches"};  // the rounds read their flags back through it
+    const UfOutcome labelled = uf_run_rounds(run, w.flags, hook, compress, &rounds);
+    if (labelled == UF_FAILED) return GTSFM_ERR_HIP;
     GTSFM_CHECK_ARG(labelled != UF_NO_FIXED_POINT, "gtsfm_tracks_from_matches: no fixed point after %d rounds (%lld nodes, %lld match rows, %d pairs); nothing was written",
                     rounds, num_nodes, total_matches, num_pairs);
     GTSFM_CHECK_ARG(labelled != UF_BAD_INPUT, "gtsfm_tracks_from_matches: an active match row names an image outside 0 .. %d or a keypoint outside its image's table; nothing was written",

@@ -21,13 +21,14 @@
 //   phase 4  aggregate  : one lane per row walks the directions in order, recomputes |w| by the same instruction sequence, reads the two
 //            positions, adds and thresholds; inlier pairs mark their cameras (plain stores of 1), then a measurement stays an inlier only
 //            when its camera is marked. The intermediate is D x G int32, not D x rows float64.
-// Every per-index step is a GTSFM_HD function that the kernels call with their global index and tools/translation_inliers_host_main.cpp calls
-// in another order and lane partition on a CPU; the atomics become plain updates there.
+// Every per-index step is a GTSFM_HD function, and the call is one function over a runner of stage_runner.h (tr_inliers_stages): the device
+// call launches its stages, tools/translation_inliers_host_main.cpp walks the same stages in another order and lane partition on a CPU,
+// where the atomics become plain updates.
 
 #include <math.h>
 
 #include "../../include/gtsfm_amd.h"
-#include "graph_prims.h"
+#include "stage_runner.h"
 
 #define TR_THREADS 256
 #define TR_WAVE 64
@@ -309,49 +310,6 @@ GTSFM_HD void tr_position_out(const TrGraph& g, long long i, int num_nodes, int*
     position[i] = g.w.cid[n + 1] > g.w.cid[n] ? g.w.pos[k * num_nodes + g.w.cid[n]] : -1;
 }
 
-// ---- kernels ----
-
-#define TR_INDEX const long long i = (long long)blockIdx.x * TR_THREADS + threadIdx.x
-
-__global__ __launch_bounds__(TR_THREADS) void tr_init_kernel(TrGraph g, long long n, uint8_t* __restrict__ camera_inlier) {
-    TR_INDEX;
-    if (i < n) tr_init(g, i, camera_inlier);
-}
-__global__ __launch_bounds__(TR_THREADS) void tr_edge_table_kernel(TrGraph g) {
-    TR_INDEX;
-    if (i < tr_rows(g)) tr_edge_table(g, i);
-}
-__global__ __launch_bounds__(TR_THREADS) void tr_node_flag_kernel(TrGraph g) {
-    TR_INDEX;
-    if (i < tr_nodes(g)) tr_node_flag(g, i);
-}
-__global__ __launch_bounds__(TR_THREADS) void tr_node_compact_kernel(TrGraph g, long long node_capacity) {
-    TR_INDEX;
-    if (i <= tr_nodes(g)) tr_node_compact(g, i, node_capacity);
-}
-__global__ __launch_bounds__(TR_THREADS) void tr_edge_fill_kernel(TrGraph g) {
-    TR_INDEX;
-    if (i < tr_rows(g)) tr_edge_fill(g, i);
-}
-__global__ __launch_bounds__(TR_THREADS) void tr_slot_rank_kernel(TrGraph g) {
-    TR_INDEX;
-    if (i < 2 * tr_rows(g)) tr_slot_rank(g, i);
-}
-__global__ __launch_bounds__(TR_THREADS) void tr_row_aggregate_kernel(TrGraph g, int num_nodes, double threshold, double* __restrict__ pair_weight,
-                                                                       double* __restrict__ meas_weight, uint8_t* __restrict__ pair_inlier,
-                                                                       uint8_t* __restrict__ meas_inlier, uint8_t* __restrict__ camera_inlier) {
-    TR_INDEX;
-    if (i < tr_rows(g)) tr_row_aggregate(g, i, num_nodes, threshold, pair_weight, meas_weight, pair_inlier, meas_inlier, camera_inlier);
-}
-__global__ __launch_bounds__(TR_THREADS) void tr_meas_filter_kernel(TrGraph g, const uint8_t* __restrict__ camera_inlier, uint8_t* __restrict__ meas_inlier) {
-    TR_INDEX;
-    if (i < g.num_meas) tr_meas_filter(g, i, camera_inlier, meas_inlier);
-}
-__global__ __launch_bounds__(TR_THREADS) void tr_position_out_kernel(TrGraph g, int num_nodes, long long n, int* __restrict__ position) {
-    TR_INDEX;
-    if (i < n) tr_position_out(g, i, num_nodes, position);
-}
-
 // One workgroup per direction, gridDim.x workgroups walking the directions. num_nodes, the step count and the direction index are uniform:
 // the barriers stay matched. Dynamic LDS: 3 * num_nodes doubles when use_lds.
 __global__ __launch_bounds__(TR_THREADS) void tr_mfas_kernel(TrGraph g, int num_nodes, int use_lds, long long node_capacity) {
@@ -385,6 +343,23 @@ __global__ __launch_bounds__(TR_THREADS) void tr_mfas_kernel(TrGraph g, int num_
         }
     }
 }
+// its stand-in on a CPU: one workgroup at a time, so every direction takes the first state slice; one lane, or the device's 256
+void tr_mfas_host(const HostRunner& run, const TrGraph& g, int num_nodes) {
+    const int lanes = run.device_lanes ? TR_THREADS : 1;
+    TrKey keys[TR_THREADS];
+    run.walk(g.num_directions, [&](long long k) {
+        double* base = g.w.state;
+        const TrState st = {base, base + num_nodes, base + 2 * (size_t)num_nodes, g.w.pos + k * num_nodes};
+        const double* d = g.directions + 3 * k;
+        run.walk(lanes, [&](long long lane) { tr_mfas_init_lane(g, st, d, num_nodes, (int)lane, lanes); });
+        for (int step = 0; step < num_nodes; ++step) {
+            run.walk(lanes, [&](long long lane) { keys[lane] = tr_mfas_lane_best(st, num_nodes, (int)lane, lanes); });
+            TrKey key = keys[run.descending ? lanes - 1 : 0];
+            run.walk(lanes, [&](long long lane) { key = tr_key_max(key, keys[lane]); });
+            if (key.id < num_nodes) run.walk(lanes, [&](long long lane) { tr_mfas_update_lane(g, st, d, key.id, step, (int)lane, lanes); });
+        }
+    });
+}
 
 // the counts: one workgroup walks the rows (integer sums by a tree, no atomics on one word)
 __global__ __launch_bounds__(SCAN_THREADS) void tr_counts_kernel(TrGraph g, int num_nodes, const uint8_t* __restrict__ pair_inlier, const uint8_t* __restrict__ meas_inlier,
@@ -402,11 +377,75 @@ __global__ __launch_bounds__(SCAN_THREADS) void tr_counts_kernel(TrGraph g, int 
         counts[6] = counts[7] = 0;
     }
 }
+// its stand-in on a CPU
+void tr_counts_host(const HostRunner& run, const TrGraph& g, int num_nodes, const uint8_t* pair_inlier, const uint8_t* meas_inlier, const uint8_t* camera_inlier,
+                    int* counts) {
+    memset(counts, 0, 8 * sizeof(int));
+    counts[2] = num_nodes;
+    run.walk(g.num_pairs, [&](long long m) { counts[0] += g.w.key1[m] >= 0 ? 1 : 0, counts[3] += pair_inlier[m] ? 1 : 0; });
+    run.walk(g.num_meas, [&](long long s) { counts[1] += g.w.key1[g.num_pairs + s] >= 0 ? 1 : 0, counts[4] += meas_inlier[s] ? 1 : 0; });
+    run.walk(g.num_images, [&](long long c) { counts[5] += camera_inlier[c] ? 1 : 0; });
+}
 
 bool tr_sizes_ok(long long num_pairs, long long num_meas, long long num_images, long long num_tracks, long long num_directions, long long node_capacity) {
     return num_pairs >= 0 && num_meas >= 0 && num_images >= 0 && num_tracks >= 0 && num_directions >= 0 && node_capacity >= 0 && num_pairs + num_meas < TR_MAX_ROWS &&
            num_images + num_tracks < TR_MAX_NODES && num_directions < TR_MAX_DIRECTIONS && node_capacity <= num_images + num_tracks &&
            (num_directions == 0 || node_capacity < (1ll << 31) / num_directions);
+}
+
+// ---- the pipeline: every stage once, for the device call and for tools/translation_inliers_host_main.cpp (stage_runner.h) ----
+
+// g.w is laid out for node_capacity nodes with an edge and lds_node_limit
+template <class Runner>
+int tr_inliers_stages(Runner& run, const char* me, const TrGraph& g, double threshold, long long node_capacity, int lds_node_limit, double* pair_weight,
+                      double* meas_weight, uint8_t* pair_inlier, uint8_t* meas_inlier, uint8_t* camera_inlier, int* position, int* counts) {
+    const long long rows = tr_rows(g), nodes = tr_nodes(g);
+    GTSFM_CHECK_ARG(g.num_directions > 0 || rows == 0, "%s: no projection direction for %lld rows; nothing was written", me, rows);
+    run.template each<struct tr_init_stage>(nodes + 1 > TR_FLAG_WORDS ? nodes + 1 : TR_FLAG_WORDS, STAGE_FN(long long i) { tr_init(g, i, camera_inlier); });
+    run.template each<struct tr_edge_table_stage>(rows, STAGE_FN(long long i) { tr_edge_table(g, i); });
+    run.template each<struct tr_node_flag_stage>(nodes, STAGE_FN(long long i) { tr_node_flag(g, i); });
+    run.scan(g.w.row_off, nodes);
+    run.scan(g.w.cid, nodes);
+    run.template each<struct tr_node_compact_stage>(nodes + 1, STAGE_FN(long long i) { tr_node_compact(g, i, node_capacity); });
+    run.template each<struct tr_edge_fill_stage>(rows, STAGE_FN(long long i) { tr_edge_fill(g, i); });
+    run.template each<struct tr_slot_rank_stage>(2 * rows, STAGE_FN(long long i) { tr_slot_rank(g, i); });
+    int flags[4] = {0, 0, 0, 0};
+    long long graph_nodes = -1;
+    run.copy(flags, g.w.flags, 4, "building the adjacency");
+    if (run.fetch(&graph_nodes, g.w.cid + nodes, 1, "building the adjacency") != GTSFM_OK) return run.status;
+    GTSFM_CHECK_ARG(!flags[0], "%s: an enabled pair row has i1 >= i2 or names an image outside 0 .. %d", me, g.num_images - 1);
+    GTSFM_CHECK_ARG(!flags[2], "%s: an enabled measurement names a camera outside 0 .. %d", me, g.num_images - 1);
+    GTSFM_CHECK_ARG(!flags[3], "%s: an enabled measurement's camera has no valid rotation", me);
+    GTSFM_CHECK_ARG(!flags[1], "%s: a measurement is listed twice", me);
+    GTSFM_CHECK_ARG(graph_nodes >= 0 && graph_nodes <= nodes, "%s: %lld graph nodes of %lld", me, graph_nodes, nodes);
+    if (graph_nodes > node_capacity) {
+        gtsfm_set_error("%s: %lld nodes have an edge, the workspace holds %lld (node_capacity)", me, graph_nodes, node_capacity);
+        return GTSFM_ERR_WORKSPACE;
+    }
+    const int num_nodes = (int)graph_nodes;
+    const int use_lds = graph_nodes <= tr_lds_limit(lds_node_limit) ? 1 : 0;
+    GTSFM_CHECK_ARG(use_lds || node_capacity > tr_lds_limit(lds_node_limit), "%s: internal: no state slice", me);
+    if (num_nodes > 0)
+        run.block(
+            "tr_mfas_kernel",
+            [&](hipStream_t stream) {
+                hipLaunchKernelGGL(tr_mfas_kernel, dim3((unsigned)tr_groups(g.num_directions)), dim3(TR_THREADS), use_lds ? (size_t)3 * num_nodes * sizeof(double) : 0, stream, g,
+                                   num_nodes, use_lds, node_capacity);
+            },
+            [&](const HostRunner& host) { tr_mfas_host(host, g, num_nodes); });
+    run.template each<struct tr_row_aggregate_stage>(rows, STAGE_FN(long long i) {
+        tr_row_aggregate(g, i, num_nodes, threshold, pair_weight, meas_weight, pair_inlier, meas_inlier, camera_inlier);
+    });
+    run.template each<struct tr_meas_filter_stage>(g.num_meas, STAGE_FN(long long i) { tr_meas_filter(g, i, camera_inlier, meas_inlier); });
+    run.block(
+        "tr_counts_kernel",
+        [&](hipStream_t stream) {
+            hipLaunchKernelGGL(tr_counts_kernel, dim3(1), dim3(SCAN_THREADS), 0, stream, g, num_nodes, pair_inlier, meas_inlier, camera_inlier, counts);
+        },
+        [&](const HostRunner& host) { tr_counts_host(host, g, num_nodes, pair_inlier, meas_inlier, camera_inlier, counts); });
+    if (position && g.num_directions * nodes > 0)
+        run.template each<struct tr_position_out_stage>(g.num_directions * nodes, STAGE_FN(long long i) { tr_position_out(g, i, num_nodes, position); });
+    return run.status;
 }
 
 }  // namespace
@@ -425,82 +464,25 @@ extern "C" int gtsfm_translation_inliers_f64(const int32_t* pair_images_dev, con
                                              void* workspace_dev, size_t workspace_bytes, double* world_pair_dev, double* world_meas_dev, double* pair_weight_dev,
                                              double* meas_weight_dev, uint8_t* pair_inlier_dev, uint8_t* meas_inlier_dev, uint8_t* camera_inlier_dev,
                                              int32_t* position_dev, int32_t* counts_dev, void* stream_) {
-    hipStream_t stream = (hipStream_t)stream_;
     const char* me = "gtsfm_translation_inliers_f64";
     GTSFM_CHECK_ARG(tr_sizes_ok(num_pairs, num_meas, num_images, num_tracks, num_directions, node_capacity),
                     "%s: sizes out of range (%lld pairs, %lld measurements, %d images, %lld tracks, %lld directions, node capacity %lld)", me, num_pairs, num_meas, num_images,
                     num_tracks, num_directions, node_capacity);
     GTSFM_CHECK_ARG(counts_dev && workspace_dev && (num_images == 0 || camera_inlier_dev), "%s: null pointer", me);
-    GTSFM_CHECK_ARG(((uintptr_t)workspace_dev & 255) == 0, "%s: the workspace must be aligned to 256 bytes", me);
     GTSFM_CHECK_ARG(num_pairs == 0 || (pair_images_dev && world_pair_dev && pair_weight_dev && pair_inlier_dev && (directions_given || (pair_direction_dev && rotation_dev && rotation_valid_dev))),
                     "%s: null pair pointer", me);
     GTSFM_CHECK_ARG(num_meas == 0 || (num_tracks > 0 && track_off_dev && image_dev && track_enable_dev && world_meas_dev && meas_weight_dev && meas_inlier_dev &&
                                       (directions_given || (uv_dev && rotation_dev && rotation_valid_dev && intrinsics_dev))),
                     "%s: null measurement pointer", me);
     GTSFM_CHECK_ARG(num_directions == 0 || directions_dev, "%s: null directions_dev", me);
-    GTSFM_CHECK_ARG(num_directions > 0 || num_pairs + num_meas == 0, "%s: no projection direction for %lld rows; nothing was written", me, num_pairs + num_meas);
     const long long rows = num_pairs + num_meas, nodes = (long long)num_images + num_tracks;
     TrGraph g{pair_images_dev, pair_direction_dev, pair_enable_dev, rotation_dev, rotation_valid_dev, intrinsics_dev, track_off_dev, image_dev, uv_dev, track_enable_dev,
               meas_enable_dev, directions_dev, num_pairs, num_meas, num_tracks, num_directions, num_images, directions_given ? 1 : 0, world_pair_dev, world_meas_dev,
               tr_layout(workspace_dev, rows, nodes, num_directions, node_capacity, lds_node_limit)};
-    if (workspace_bytes < g.w.bytes) {
-        gtsfm_set_error("%s: workspace of %zu bytes, %zu needed for %lld rows, %lld nodes, %lld directions and a node capacity of %lld", me, workspace_bytes, g.w.bytes, rows,
-                        nodes, num_directions, node_capacity);
-        return GTSFM_ERR_WORKSPACE;
-    }
-    const dim3 threads(TR_THREADS), row_grid = launch_grid(rows, TR_THREADS), node_grid = launch_grid(nodes + 1, TR_THREADS), scan(SCAN_THREADS);
-    const long long init_n = nodes + 1 > TR_FLAG_WORDS ? nodes + 1 : TR_FLAG_WORDS;
-
-    hipLaunchKernelGGL(tr_init_kernel, launch_grid(init_n, TR_THREADS), threads, 0, stream, g, init_n, camera_inlier_dev);
-    GTSFM_CHECK_LAUNCH("tr_init_kernel");
-    hipLaunchKernelGGL(tr_edge_table_kernel, row_grid, threads, 0, stream, g);
-    GTSFM_CHECK_LAUNCH("tr_edge_table_kernel");
-    hipLaunchKernelGGL(tr_node_flag_kernel, node_grid, threads, 0, stream, g);
-    GTSFM_CHECK_LAUNCH("tr_node_flag_kernel");
-    hipLaunchKernelGGL(scan_one_workgroup_kernel<long long>, dim3(1), scan, 0, stream, g.w.row_off, nodes);
-    GTSFM_CHECK_LAUNCH("scan_one_workgroup_kernel");
-    hipLaunchKernelGGL(scan_one_workgroup_kernel<long long>, dim3(1), scan, 0, stream, g.w.cid, nodes);
-    GTSFM_CHECK_LAUNCH("scan_one_workgroup_kernel");
-    hipLaunchKernelGGL(tr_node_compact_kernel, node_grid, threads, 0, stream, g, node_capacity);
-    GTSFM_CHECK_LAUNCH("tr_node_compact_kernel");
-    hipLaunchKernelGGL(tr_edge_fill_kernel, row_grid, threads, 0, stream, g);
-    GTSFM_CHECK_LAUNCH("tr_edge_fill_kernel");
-    hipLaunchKernelGGL(tr_slot_rank_kernel, launch_grid(2 * rows, TR_THREADS), threads, 0, stream, g);
-    GTSFM_CHECK_LAUNCH("tr_slot_rank_kernel");
-    int flags[4] = {0, 0, 0, 0};
-    long long graph_nodes = -1;
-    if (hipMemcpyAsync(flags, g.w.flags, sizeof(flags), hipMemcpyDeviceToHost, stream) != hipSuccess ||
-        hipMemcpyAsync(&graph_nodes, g.w.cid + nodes, 8, hipMemcpyDeviceToHost, stream) != hipSuccess || hipStreamSynchronize(stream) != hipSuccess) {
-        gtsfm_set_error("%s: building the adjacency failed: %s", me, hipGetErrorString(hipGetLastError()));
-        return GTSFM_ERR_HIP;
-    }
-    GTSFM_CHECK_ARG(!flags[0], "%s: an enabled pair row has i1 >= i2 or names an image outside 0 .. %d", me, num_images - 1);
-    GTSFM_CHECK_ARG(!flags[2], "%s: an enabled measurement names a camera outside 0 .. %d", me, num_images - 1);
-    GTSFM_CHECK_ARG(!flags[3], "%s: an enabled measurement's camera has no valid rotation", me);
-    GTSFM_CHECK_ARG(!flags[1], "%s: a measurement is listed twice", me);
-    GTSFM_CHECK_ARG(graph_nodes >= 0 && graph_nodes <= nodes, "%s: %lld graph nodes of %lld", me, graph_nodes, nodes);
-    if (graph_nodes > node_capacity) {
-        gtsfm_set_error("%s: %lld nodes have an edge, the workspace holds %lld (node_capacity)", me, graph_nodes, node_capacity);
-        return GTSFM_ERR_WORKSPACE;
-    }
-    const int num_nodes = (int)graph_nodes;
-    const int use_lds = graph_nodes <= tr_lds_limit(lds_node_limit) ? 1 : 0;
-    GTSFM_CHECK_ARG(use_lds || node_capacity > tr_lds_limit(lds_node_limit), "%s: internal: no state slice", me);
-    if (num_nodes > 0) {
-        hipLaunchKernelGGL(tr_mfas_kernel, dim3((unsigned)tr_groups(num_directions)), threads, use_lds ? (size_t)3 * num_nodes * sizeof(double) : 0, stream, g, num_nodes,
-                           use_lds, node_capacity);
-        GTSFM_CHECK_LAUNCH("tr_mfas_kernel");
-    }
-    hipLaunchKernelGGL(tr_row_aggregate_kernel, row_grid, threads, 0, stream, g, num_nodes, threshold, pair_weight_dev, meas_weight_dev, pair_inlier_dev, meas_inlier_dev,
-                       camera_inlier_dev);
-    GTSFM_CHECK_LAUNCH("tr_row_aggregate_kernel");
-    hipLaunchKernelGGL(tr_meas_filter_kernel, launch_grid(num_meas, TR_THREADS), threads, 0, stream, g, camera_inlier_dev, meas_inlier_dev);
-    GTSFM_CHECK_LAUNCH("tr_meas_filter_kernel");
-    hipLaunchKernelGGL(tr_counts_kernel, dim3(1), scan, 0, stream, g, num_nodes, pair_inlier_dev, meas_inlier_dev, camera_inlier_dev, counts_dev);
-    GTSFM_CHECK_LAUNCH("tr_counts_kernel");
-    if (position_dev && num_directions * nodes > 0) {
-        hipLaunchKernelGGL(tr_position_out_kernel, launch_grid(num_directions * nodes, TR_THREADS), threads, 0, stream, g, num_nodes, num_directions * nodes, position_dev);
-        GTSFM_CHECK_LAUNCH("tr_position_out_kernel");
-    }
-    return GTSFM_OK;
+    const int fits = gtsfm_check_workspace(me, workspace_dev, workspace_bytes >= g.w.bytes, workspace_bytes, g.w.bytes, "%lld rows, %lld nodes, %lld directions and a node capacity of %lld", rows, nodes,
+                                           num_directions, node_capacity);
+    if (fits != GTSFM_OK) return fits;
+    DeviceRunner run{(hipStream_t)stream_, me};
+    return tr_inliers_stages(run, me, g, threshold, node_capacity, lds_node_limit, pair_weight_dev, meas_weight_dev, pair_inlier_dev, meas_inlier_dev, camera_inlier_dev,
+                             position_dev, counts_dev);
 }

@@ -18,6 +18,8 @@
 //                code, same bits) for the inlier mask; then the n-view DLT, refinement, errors, angle test and exit code.
 // Every sum over a track's measurements is a serial loop in measurement order inside one lane: no atomics, no cross-lane reduction, so
 // the outputs of a track depend on that track's data and the options only -- not on the batch, the grid or the run.
+// The stages are one function over a runner of stage_runner.h (tri_triangulate_stages): the device call launches them,
+// tools/triangulation_host_main.cpp walks the same function on a CPU.
 //
 // DLT without squaring the condition number: the rows u P2 - P0, v P2 - P1 are rotated one by one into a 4 x 4 upper triangle (Givens,
 // O(1) state for any track length), whose singular values and last right singular vector come from a one-sided Jacobi (Hestenes) with
@@ -26,7 +28,7 @@
 #include <math.h>
 
 #include "../../include/gtsfm_amd.h"
-#include "common.h"
+#include "stage_runner.h"
 
 #define TRI_THREADS 256
 #define TRI_FINAL_THREADS 64  // one wave per workgroup: 11 789 tracks spread over 185 CUs instead of 47
@@ -411,11 +413,6 @@ TRI_HD void tri_count_track(long long t, const long long* __restrict__ track_off
     hyp_off[t] = mode == TRI_NO_RANSAC ? 0 : (pairs < num_hyp ? pairs : num_hyp);
 }
 
-__global__ __launch_bounds__(TRI_THREADS) void tri_count_kernel(const long long* __restrict__ track_off, long long num_tracks, long long total, int mode,
-                                                                long long num_hyp, long long* __restrict__ hyp_off, int* flags) {
-    tri_count_track((long long)blockIdx.x * TRI_THREADS + threadIdx.x, track_off, num_tracks, total, mode, num_hyp, hyp_off, flags);
-}
-
 // one workgroup: val[0 .. n) -> its exclusive scan in place, val[n] = the total
 __global__ __launch_bounds__(TRI_THREADS) void tri_scan_kernel(long long* val, long long n, long long cap, int* flags) {
     __shared__ long long lds[TRI_THREADS];
@@ -440,6 +437,11 @@ __global__ __launch_bounds__(TRI_THREADS) void tri_scan_kernel(long long* val, l
         val[n] = carry;
         if (carry > cap) flags[1] = 1;
     }
+}
+// its stand-in on a CPU
+void tri_scan_host(const HostRunner& run, long long* val, long long n, long long cap, int* flags) {
+    run.scan(val, n);
+    if (val[n] > cap) flags[1] = 1;
 }
 
 TRI_HD inline unsigned long long tri_float_bits(float f) {
@@ -482,15 +484,6 @@ TRI_HD void tri_select_track(long long t, int first_pair, int stride, const long
             }
         if (rank < num_hyp && first + rank < cap) sel[first + rank] = p;
     }
-}
-
-// one workgroup per track
-__global__ __launch_bounds__(TRI_THREADS) void tri_select_kernel(const long long* __restrict__ track_off, const int* __restrict__ track_image,
-                                                                 const float* __restrict__ track_uv, const double* __restrict__ cams, int num_images,
-                                                                 int mode, long long num_hyp, unsigned long long seed,
-                                                                 const long long* __restrict__ hyp_off, int* __restrict__ sel, long long cap,
-                                                                 const int* __restrict__ flags) {
-    tri_select_track(blockIdx.x, threadIdx.x, TRI_THREADS, track_off, track_image, track_uv, cams, num_images, mode, num_hyp, seed, hyp_off, sel, cap, flags);
 }
 
 // hypotheses first, first + stride, ... of the whole batch
@@ -539,16 +532,6 @@ TRI_HD void tri_hypothesis_lane(long long first_hyp, long long stride, const lon
         }
         hyp[g] = out;
     }
-}
-
-__global__ __launch_bounds__(TRI_THREADS) void tri_hypothesis_kernel(const long long* __restrict__ track_off, const int* __restrict__ track_image,
-                                                                     const float* __restrict__ track_uv, long long num_tracks,
-                                                                     const double* __restrict__ cams, int num_images, double threshold,
-                                                                     long long num_hyp, const long long* __restrict__ hyp_off,
-                                                                     const int* __restrict__ sel, TriHyp* __restrict__ hyp, long long cap,
-                                                                     const int* __restrict__ flags) {
-    tri_hypothesis_lane((long long)blockIdx.x * TRI_THREADS + threadIdx.x, (long long)gridDim.x * TRI_THREADS, track_off, track_image, track_uv, num_tracks, cams,
-                        num_images, threshold, num_hyp, hyp_off, sel, hyp, cap, flags);
 }
 
 TRI_HD void tri_final_track(long long t, const long long* __restrict__ track_off, const int* __restrict__ track_image,
@@ -679,15 +662,51 @@ TRI_HD void tri_final_track(long long t, const long long* __restrict__ track_off
     exit_code[t] = code;
 }
 
-__global__ __launch_bounds__(TRI_THREADS) void tri_final_kernel(const long long* __restrict__ track_off, const int* __restrict__ track_image,
-                                                                const float* __restrict__ track_uv, long long num_tracks,
-                                                                const double* __restrict__ cams, int num_images, int mode, double threshold,
-                                                                double min_angle_deg, const long long* __restrict__ hyp_off,
-                                                                const TriHyp* __restrict__ hyp, long long cap, const int* __restrict__ flags,
-                                                                double* __restrict__ point, double* __restrict__ avg_error, int* __restrict__ exit_code,
-                                                                uint8_t* inlier_mask, int* __restrict__ stats) {
-    tri_final_track((long long)blockIdx.x * blockDim.x + threadIdx.x, track_off, track_image, track_uv, num_tracks, cams, num_images, mode, threshold,
-                    min_angle_deg, hyp_off, hyp, cap, flags, point, avg_error, exit_code, inlier_mask, stats);
+// ---- the pipeline: every stage once, for the device call and for tools/triangulation_host_main.cpp (stage_runner.h) ----
+
+struct TriCall {  // the checked arguments; max_hyp is 0 without RANSAC
+    const long long* track_off;
+    const int* image;
+    const float* uv;
+    long long num_tracks, total;
+    const double* cams;
+    int num_images, mode;
+    double threshold, min_angle_deg;
+    long long max_hyp;
+    unsigned long long seed;
+    double *point, *avg_error;
+    int* exit_code;
+    uint8_t* inlier_mask;
+    int* stats;
+};
+
+// at least one track; w is laid out for c.num_tracks, c.total and c.max_hyp
+template <class Runner>
+int tri_triangulate_stages(Runner& run, const char* me, const TriCall& c, const TriWorkspace& w) {
+    run.zero(w.flags, 16);
+    run.template each<struct tri_count_stage>(c.num_tracks, STAGE_FN(long long t) { tri_count_track(t, c.track_off, c.num_tracks, c.total, c.mode, c.max_hyp, w.hyp_off, w.flags); });
+    run.block(
+        "tri_scan_kernel", [&](hipStream_t stream) { hipLaunchKernelGGL(tri_scan_kernel, dim3(1), dim3(TRI_THREADS), 0, stream, w.hyp_off, c.num_tracks, w.cap, w.flags); },
+        [&](const HostRunner& host) { tri_scan_host(host, w.hyp_off, c.num_tracks, w.cap, w.flags); });
+    if (c.mode != TRI_NO_RANSAC) {
+        run.template group<struct tri_select_stage, TRI_THREADS, TRI_THREADS>(c.num_tracks, STAGE_FN(long long t, int lane, int lanes) {
+            tri_select_track(t, lane, lanes, c.track_off, c.image, c.uv, c.cams, c.num_images, c.mode, c.max_hyp, c.seed, w.hyp_off, w.sel, w.cap, w.flags);
+        });
+        const long long want = (w.cap + TRI_THREADS - 1) / TRI_THREADS, groups = want < TRI_HYP_BLOCKS ? want : TRI_HYP_BLOCKS;
+        run.template group<struct tri_hypothesis_stage, TRI_THREADS, TRI_THREADS>(groups, STAGE_FN(long long group, int lane, int lanes) {
+            tri_hypothesis_lane(group * lanes + lane, groups * lanes, c.track_off, c.image, c.uv, c.num_tracks, c.cams, c.num_images, c.threshold, c.max_hyp, w.hyp_off, w.sel,
+                                w.hyp, w.cap, w.flags);
+        });
+    }
+    run.template each<struct tri_final_stage, TRI_FINAL_THREADS, TRI_THREADS>(c.num_tracks, STAGE_FN(long long t) {
+        tri_final_track(t, c.track_off, c.image, c.uv, c.num_tracks, c.cams, c.num_images, c.mode, c.threshold, c.min_angle_deg, w.hyp_off, w.hyp, w.cap, w.flags, c.point,
+                        c.avg_error, c.exit_code, c.inlier_mask, c.stats);
+    });
+    int flag[2] = {0, 0};
+    if (run.fetch(flag, w.flags, 2, "reading the flags") != GTSFM_OK) return run.status;
+    GTSFM_CHECK_ARG(!flag[0], "%s: track_off_dev is not ascending within 0 .. %lld, or a track is longer than %d; nothing was written", me, c.total, TRI_MAX_TRACK_LENGTH);
+    GTSFM_CHECK_ARG(!flag[1], "%s: the tracks hold more than %lld measurements; nothing was written", me, c.total);
+    return run.status;
 }
 
 }  // namespace
@@ -703,58 +722,25 @@ extern "C" int gtsfm_triangulate_tracks_f64(const long long* track_off_dev, cons
                                             double reproj_error_threshold, double min_triangulation_angle_deg, long long num_hypotheses,
                                             unsigned long long seed, void* workspace_dev, size_t workspace_bytes, double* point_dev,
                                             double* avg_error_dev, int32_t* exit_code_dev, uint8_t* inlier_mask_dev, int32_t* stats_dev, void* stream_) {
-    hipStream_t stream = (hipStream_t)stream_;
+    const char* me = "gtsfm_triangulate_tracks_f64";
     GTSFM_CHECK_ARG(num_tracks >= 0 && total_measurements >= 0 && num_images >= 0 && num_tracks < (1ll << 31) && total_measurements < (1ll << 40),
-                    "gtsfm_triangulate_tracks_f64: size out of range (%lld tracks, %lld measurements, %d images)", num_tracks, total_measurements, num_images);
-    GTSFM_CHECK_ARG(mode >= TRI_NO_RANSAC && mode <= TRI_TOPK, "gtsfm_triangulate_tracks_f64: mode %d outside 0 .. 3", mode);
-    GTSFM_CHECK_ARG(reproj_error_threshold > 0.0, "gtsfm_triangulate_tracks_f64: reproj_error_threshold %g must be positive (infinity allowed)",
-                    reproj_error_threshold);
-    GTSFM_CHECK_ARG(min_triangulation_angle_deg == min_triangulation_angle_deg, "gtsfm_triangulate_tracks_f64: min_triangulation_angle_deg is NaN");
-    GTSFM_CHECK_ARG(mode == TRI_NO_RANSAC || num_hypotheses >= 0, "gtsfm_triangulate_tracks_f64: %lld hypotheses", num_hypotheses);
+                    "%s: size out of range (%lld tracks, %lld measurements, %d images)", me, num_tracks, total_measurements, num_images);
+    GTSFM_CHECK_ARG(mode >= TRI_NO_RANSAC && mode <= TRI_TOPK, "%s: mode %d outside 0 .. 3", me, mode);
+    GTSFM_CHECK_ARG(reproj_error_threshold > 0.0, "%s: reproj_error_threshold %g must be positive (infinity allowed)", me, reproj_error_threshold);
+    GTSFM_CHECK_ARG(min_triangulation_angle_deg == min_triangulation_angle_deg, "%s: min_triangulation_angle_deg is NaN", me);
+    GTSFM_CHECK_ARG(mode == TRI_NO_RANSAC || num_hypotheses >= 0, "%s: %lld hypotheses", me, num_hypotheses);
     if (num_tracks == 0) return GTSFM_OK;
-    GTSFM_CHECK_ARG(track_off_dev && point_dev && avg_error_dev && exit_code_dev && stats_dev && workspace_dev, "gtsfm_triangulate_tracks_f64: null pointer");
-    GTSFM_CHECK_ARG(total_measurements == 0 || (track_image_dev && track_uv_dev && inlier_mask_dev), "gtsfm_triangulate_tracks_f64: null measurement pointer");
-    GTSFM_CHECK_ARG(num_images == 0 || cameras_dev, "gtsfm_triangulate_tracks_f64: null camera table");
-    GTSFM_CHECK_ARG(((uintptr_t)workspace_dev & 255) == 0, "gtsfm_triangulate_tracks_f64: the workspace must be aligned to 256 bytes");
+    GTSFM_CHECK_ARG(track_off_dev && point_dev && avg_error_dev && exit_code_dev && stats_dev && workspace_dev, "%s: null pointer", me);
+    GTSFM_CHECK_ARG(total_measurements == 0 || (track_image_dev && track_uv_dev && inlier_mask_dev), "%s: null measurement pointer", me);
+    GTSFM_CHECK_ARG(num_images == 0 || cameras_dev, "%s: null camera table", me);
     const long long max_hyp = mode == TRI_NO_RANSAC ? 0 : num_hypotheses;
     const TriWorkspace w = tri_layout(workspace_dev, num_tracks, total_measurements, max_hyp);
-    if (w.cap < 0 || workspace_bytes < w.bytes) {
-        gtsfm_set_error("gtsfm_triangulate_tracks_f64: workspace of %zu bytes, %zu needed for %lld tracks / %lld measurements / %lld hypotheses", workspace_bytes,
-                        w.bytes, num_tracks, total_measurements, max_hyp);
-        return GTSFM_ERR_WORKSPACE;
-    }
-    if (hipMemsetAsync(w.flags, 0, 16, stream) != hipSuccess) {
-        gtsfm_set_error("gtsfm_triangulate_tracks_f64: hipMemsetAsync failed: %s", hipGetErrorString(hipGetLastError()));
-        return GTSFM_ERR_HIP;
-    }
-    const dim3 threads(TRI_THREADS);
-    const dim3 track_grid((unsigned)((num_tracks + TRI_THREADS - 1) / TRI_THREADS));
-    hipLaunchKernelGGL(tri_count_kernel, track_grid, threads, 0, stream, track_off_dev, num_tracks, total_measurements, mode, max_hyp, w.hyp_off, w.flags);
-    GTSFM_CHECK_LAUNCH("tri_count_kernel");
-    hipLaunchKernelGGL(tri_scan_kernel, dim3(1), threads, 0, stream, w.hyp_off, num_tracks, w.cap, w.flags);
-    GTSFM_CHECK_LAUNCH("tri_scan_kernel");
-    if (mode != TRI_NO_RANSAC) {
-        hipLaunchKernelGGL(tri_select_kernel, dim3((unsigned)num_tracks), threads, 0, stream, track_off_dev, track_image_dev, track_uv_dev, cameras_dev, num_images,
-                           mode, max_hyp, seed, w.hyp_off, w.sel, w.cap, w.flags);
-        GTSFM_CHECK_LAUNCH("tri_select_kernel");
-        const long long want = (w.cap + TRI_THREADS - 1) / TRI_THREADS;
-        hipLaunchKernelGGL(tri_hypothesis_kernel, dim3((unsigned)(want < TRI_HYP_BLOCKS ? want : TRI_HYP_BLOCKS)), threads, 0, stream, track_off_dev,
-                           track_image_dev, track_uv_dev, num_tracks, cameras_dev, num_images, reproj_error_threshold, max_hyp, w.hyp_off, w.sel, w.hyp, w.cap,
-                           w.flags);
-        GTSFM_CHECK_LAUNCH("tri_hypothesis_kernel");
-    }
-    const dim3 final_grid((unsigned)((num_tracks + TRI_FINAL_THREADS - 1) / TRI_FINAL_THREADS));
-    hipLaunchKernelGGL(tri_final_kernel, final_grid, dim3(TRI_FINAL_THREADS), 0, stream, track_off_dev, track_image_dev, track_uv_dev, num_tracks, cameras_dev, num_images, mode,
-                       reproj_error_threshold, min_triangulation_angle_deg, w.hyp_off, w.hyp, w.cap, w.flags, point_dev, avg_error_dev, exit_code_dev,
-                       inlier_mask_dev, stats_dev);
-    GTSFM_CHECK_LAUNCH("tri_final_kernel");
-    int flag[2] = {0, 0};
-    if (hipMemcpyAsync(flag, w.flags, sizeof(flag), hipMemcpyDeviceToHost, stream) != hipSuccess || hipStreamSynchronize(stream) != hipSuccess) {
-        gtsfm_set_error("gtsfm_triangulate_tracks_f64: failed: %s", hipGetErrorString(hipGetLastError()));
-        return GTSFM_ERR_HIP;
-    }
-    GTSFM_CHECK_ARG(!flag[0], "gtsfm_triangulate_tracks_f64: track_off_dev is not ascending within 0 .. %lld, or a track is longer than %d; nothing was written",
-                    total_measurements, TRI_MAX_TRACK_LENGTH);
-    GTSFM_CHECK_ARG(!flag[1], "gtsfm_triangulate_tracks_f64: the tracks hold more than %lld measurements; nothing was written", total_measurements);
-    return GTSFM_OK;
+    // a hypothesis capacity beyond 4e18 (w.cap < 0) fits no workspace
+    const int fits = gtsfm_check_workspace(me, workspace_dev, w.cap >= 0 && workspace_bytes >= w.bytes, workspace_bytes, w.bytes, "%lld tracks / %lld measurements / %lld hypotheses", num_tracks,
+                                           total_measurements, max_hyp);
+    if (fits != GTSFM_OK) return fits;
+    const TriCall c{track_off_dev, track_image_dev, track_uv_dev, num_tracks, total_measurements, cameras_dev, num_images, mode, reproj_error_threshold,
+                    min_triangulation_angle_deg, max_hyp, seed, point_dev, avg_error_dev, exit_code_dev, inlier_mask_dev, stats_dev};
+    DeviceRunner run{(hipStream_t)stream_, me};
+    return tri_triangulate_stages(run, me, c, w);
 }

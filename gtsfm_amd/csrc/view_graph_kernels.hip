@@ -32,13 +32,14 @@
 // large ones the owner of the smallest enabled row.
 // COUNTS are taken by one workgroup that walks the rows, not by atomics on one word.
 //
-// Every per-index step is a GTSFM_HD function that the kernels call with their global index and tools/view_graph_host_main.cpp calls in
-// another order on a CPU; the atomics become plain updates there.
+// Every per-index step is a GTSFM_HD function, and each call is one function over a runner of stage_runner.h (vg_cycle_filter_stages,
+// vg_largest_component_stages): the device call launches its stages, tools/view_graph_host_main.cpp walks the same stages in another
+// order on a CPU, where the atomics become plain updates.
 
 #include <math.h>
 
 #include "../../include/gtsfm_amd.h"
-#include "graph_prims.h"
+#include "stage_runner.h"
 
 #define VG_THREADS 256
 #define VG_WAVE 64
@@ -342,62 +343,6 @@ GTSFM_HD void vg_cc_write_edge(const VgComponents& g, long long e, uint8_t* __re
     pair_keep[e] = vg_cc_edge_kept(g, e, vg_cc_root_of_key(g, *g.best)) ? 1 : 0;
 }
 
-// ---- kernels: one index per thread (one wave per edge for the aggregate) ----
-
-#define VG_INDEX const long long i = (long long)blockIdx.x * VG_THREADS + threadIdx.x
-
-__global__ __launch_bounds__(VG_THREADS) void vg_init_kernel(VgGraph g, long long n) {
-    VG_INDEX;
-    if (i < n) vg_init(g, i);
-}
-__global__ __launch_bounds__(VG_THREADS) void vg_edge_degree_kernel(VgGraph g) {
-    VG_INDEX;
-    if (i < g.num_edges) vg_edge_degree(g, i);
-}
-__global__ __launch_bounds__(VG_THREADS) void vg_edge_fill_kernel(VgGraph g) {
-    VG_INDEX;
-    if (i < g.num_edges) vg_edge_fill(g, i);
-}
-__global__ __launch_bounds__(VG_THREADS) void vg_slot_rank_kernel(VgGraph g) {
-    VG_INDEX;
-    if (i < 2 * g.num_edges) vg_slot_rank(g, i);
-}
-__global__ __launch_bounds__(VG_THREADS) void vg_slot_triplets_kernel(VgGraph g, int fill, int* __restrict__ triplets, double* __restrict__ cycle_error) {
-    VG_INDEX;
-    if (i < 2 * g.num_edges) vg_slot_triplets(g, i, fill != 0, triplets, cycle_error);
-}
-__global__ __launch_bounds__(VG_THREADS) void vg_edge_aggregate_kernel(VgGraph g, int criterion, double threshold,
-                                                                        int* __restrict__ num_triplets, double* __restrict__ aggregate,
-                                                                        uint8_t* __restrict__ keep) {
-    const long long e = (long long)blockIdx.x * (VG_THREADS / VG_WAVE) + threadIdx.x / VG_WAVE;
-    if (e < g.num_edges) vg_edge_aggregate(g, e, threadIdx.x % VG_WAVE, VG_WAVE, criterion, threshold, num_triplets, aggregate, keep);
-}
-
-__global__ __launch_bounds__(VG_THREADS) void vg_cc_init_kernel(VgComponents g, long long n) {
-    VG_INDEX;
-    if (i < n) vg_cc_init(g, i);
-}
-__global__ __launch_bounds__(VG_THREADS) void vg_cc_hook_kernel(VgComponents g, int round) {
-    VG_INDEX;
-    if (i < g.num_edges) vg_cc_hook(g, i, round);
-}
-__global__ __launch_bounds__(VG_THREADS) void vg_cc_compress_kernel(VgComponents g) {
-    VG_INDEX;
-    if (i < g.num_images) uf_compress(g.parent, g.label, i);
-}
-__global__ __launch_bounds__(VG_THREADS) void vg_cc_node_count_kernel(VgComponents g) {
-    VG_INDEX;
-    if (i < g.num_images) vg_cc_node_count(g, i);
-}
-__global__ __launch_bounds__(VG_THREADS) void vg_cc_write_node_kernel(VgComponents g, uint8_t* __restrict__ node_mask) {
-    VG_INDEX;
-    if (i < g.num_images) vg_cc_write_node(g, i, node_mask);
-}
-__global__ __launch_bounds__(VG_THREADS) void vg_cc_write_edge_kernel(VgComponents g, uint8_t* __restrict__ pair_keep) {
-    VG_INDEX;
-    if (i < g.num_edges) vg_cc_write_edge(g, i, pair_keep);
-}
-
 // ---- the counts: ONE workgroup walks the rows and combines by a tree. Tens of thousands of atomics on one word would serialise (measured:
 // 11 ns each, 1.6 ms of the aggregate kernel's 1.65 ms at 48 725 edges); a walk of the same rows by 1024 lanes does not.
 
@@ -419,6 +364,18 @@ __global__ __launch_bounds__(SCAN_THREADS) void vg_filter_counts_kernel(const ui
         counts[0] = (int)in, counts[1] = (int)kept, counts[2] = (int)total_triplets, counts[3] = (int)most;
         counts[4] = counts[5] = counts[6] = counts[7] = 0;
     }
+}
+// its stand-in on a CPU
+void vg_filter_counts_host(const HostRunner& run, const uint8_t* input, const uint8_t* keep, const int* num_triplets, long long num_edges, long long total_triplets,
+                           int* counts) {
+    long long in = 0, kept = 0, most = 0;
+    run.walk(num_edges, [&](long long e) {
+        in += input[e] ? 1 : 0;
+        kept += keep[e] ? 1 : 0;
+        most = num_triplets[e] > most ? num_triplets[e] : most;
+    });
+    memset(counts, 0, 8 * sizeof(int));
+    counts[0] = (int)in, counts[1] = (int)kept, counts[2] = (int)total_triplets, counts[3] = (int)most;
 }
 
 // the largest size and the roots over the nodes, the winning bid over the rows (stored with the size in *g.best for the two write
@@ -450,6 +407,95 @@ __global__ __launch_bounds__(SCAN_THREADS) void vg_cc_summary_kernel(VgComponent
         counts[3] = counts[4] = counts[5] = counts[6] = counts[7] = 0;
     }
 }
+// its stand-in on a CPU
+void vg_cc_summary_host(const HostRunner& run, const VgComponents& g, int* counts) {
+    vg_u64 largest = 0, components = 0, bid = 0, edges = 0;
+    run.walk(g.num_images, [&](long long v) {
+        const vg_u64 size = g.cnt[v] > 0 ? (vg_u64)g.cnt[v] : 0;
+        components += size ? 1 : 0;
+        largest = size > largest ? size : largest;
+    });
+    if (largest) run.walk(g.num_edges, [&](long long e) {
+        const vg_u64 b = vg_cc_edge_bid(g, e, (int)largest);
+        bid = b > bid ? b : bid;
+    });
+    const vg_u64 best = largest ? (largest << 32) | bid : 0;
+    const int root = vg_cc_root_of_key(g, best);
+    run.walk(g.num_edges, [&](long long e) { edges += vg_cc_edge_kept(g, e, root) ? 1 : 0; });
+    *g.best = best;
+    memset(counts, 0, 8 * sizeof(int));
+    counts[0] = (int)(best >> 32), counts[1] = (int)edges, counts[2] = (int)components;
+}
+
+// ---- the two pipelines: every stage once, for the device call and for tools/view_graph_host_main.cpp (stage_runner.h) ----
+
+// g.w is laid out for triplet_capacity triplets. With more triplets than that, *num_triplets_host tells how many and nothing is written.
+template <class Runner>
+int vg_cycle_filter_stages(Runner& run, const char* me, const VgGraph& g, int criterion, double error_threshold, long long triplet_capacity, int* num_triplets,
+                           double* aggregate_error, uint8_t* keep, int* counts, int* triplets, double* cycle_error, long long* num_triplets_host) {
+    const long long E = g.num_edges, slots = 2 * E;
+    if (E == 0) {
+        if (run.zero(counts, 8 * sizeof(int)) == GTSFM_OK && num_triplets_host) *num_triplets_host = 0;
+        return run.status;
+    }
+    const long long init_n = (long long)g.num_images + 1 > VG_FLAG_WORDS ? (long long)g.num_images + 1 : VG_FLAG_WORDS;
+    run.template each<struct vg_init_stage>(init_n, STAGE_FN(long long i) { vg_init(g, i); });
+    run.template each<struct vg_edge_degree_stage>(E, STAGE_FN(long long i) { vg_edge_degree(g, i); });
+    run.scan(g.w.row_off, g.num_images);
+    run.template each<struct vg_edge_fill_stage>(E, STAGE_FN(long long i) { vg_edge_fill(g, i); });
+    run.template each<struct vg_slot_rank_stage>(slots, STAGE_FN(long long i) { vg_slot_rank(g, i); });
+    int flags[2] = {0, 0};
+    if (run.fetch(flags, g.w.flags, 2, "building the adjacency") != GTSFM_OK) return run.status;
+    GTSFM_CHECK_ARG(!flags[0], "%s: an enabled edge has i1 >= i2 or names an image outside 0 .. %d; nothing was written", me, g.num_images - 1);
+    GTSFM_CHECK_ARG(!flags[1], "%s: an enabled edge is listed twice; nothing was written", me);
+
+    const auto slot_triplets = [&](bool fill, int* triplets_out, double* cycle_error_out) {  // one kernel, launched to count and then to fill
+        run.template each<struct vg_slot_triplets_stage>(slots, STAGE_FN(long long i) { vg_slot_triplets(g, i, fill, triplets_out, cycle_error_out); });
+    };
+    slot_triplets(false, nullptr, nullptr);
+    run.scan(g.w.seg_off, slots);
+    run.scan(g.w.trip_off, slots);
+    long long entries = -1, total = -1;  // entries of the per-edge lists, distinct triplets
+    run.copy(&entries, g.w.seg_off + slots, 1, "counting the triplets");
+    if (run.fetch(&total, g.w.trip_off + slots, 1, "counting the triplets") != GTSFM_OK) return run.status;
+    GTSFM_CHECK_ARG(total >= 0 && entries == 3 * total, "%s: %lld list entries for %lld triplets; nothing was written", me, entries, total);
+    if (num_triplets_host) *num_triplets_host = total;
+    if (total > triplet_capacity) {
+        gtsfm_set_error("%s: %lld triplets, capacity (workspace and triplet outputs) for %lld; nothing was written", me, total, triplet_capacity);
+        return GTSFM_ERR_WORKSPACE;
+    }
+
+    slot_triplets(true, triplets, cycle_error);
+    run.template group<struct vg_edge_aggregate_stage, VG_THREADS, VG_WAVE>(E, STAGE_FN(long long e, int lane, int lanes) {
+        vg_edge_aggregate(g, e, lane, lanes, criterion, error_threshold, num_triplets, aggregate_error, keep);
+    });
+    return run.block(
+        "vg_filter_counts_kernel",
+        [&](hipStream_t stream) { hipLaunchKernelGGL(vg_filter_counts_kernel, dim3(1), dim3(SCAN_THREADS), 0, stream, g.w.input, keep, num_triplets, E, total, counts); },
+        [&](const HostRunner& host) { vg_filter_counts_host(host, g.w.input, keep, num_triplets, E, total, counts); });
+}
+
+template <class Runner>
+int vg_largest_component_stages(Runner& run, const char* me, const VgComponents& g, uint8_t* node_mask, uint8_t* pair_keep, int* counts) {
+    const long long E = g.num_edges, N = g.num_images;
+    run.template each<struct vg_cc_init_stage>(N > VG_FLAG_WORDS ? N : VG_FLAG_WORDS, STAGE_FN(long long i) { vg_cc_init(g, i); });
+    if (E > 0) {
+        int rounds = 0;
+        const UfOutcome labelled = uf_run_rounds(
+            run, g.flags, [&](int round) { return run.template each<struct vg_cc_hook_stage>(E, STAGE_FN(long long i) { vg_cc_hook(g, i, round); }); },
+            [&] { return run.template each<struct vg_cc_compress_stage>(N, STAGE_FN(long long i) { uf_compress(g.parent, g.label, i); }); }, &rounds);
+        if (labelled == UF_FAILED) return run.status;
+        GTSFM_CHECK_ARG(labelled != UF_NO_FIXED_POINT, "%s: no fixed point after %d rounds (%d images, %lld edges); nothing was written", me, rounds, g.num_images, E);
+        GTSFM_CHECK_ARG(labelled != UF_BAD_INPUT, "%s: an enabled edge names an image outside 0 .. %d; nothing was written", me, g.num_images - 1);
+        run.template each<struct vg_cc_node_count_stage>(N, STAGE_FN(long long i) { vg_cc_node_count(g, i); });
+    }
+    run.block(
+        "vg_cc_summary_kernel", [&](hipStream_t stream) { hipLaunchKernelGGL(vg_cc_summary_kernel, dim3(1), dim3(SCAN_THREADS), 0, stream, g, counts); },
+        [&](const HostRunner& host) { vg_cc_summary_host(host, g, counts); });
+    run.template each<struct vg_cc_write_node_stage>(N, STAGE_FN(long long i) { vg_cc_write_node(g, i, node_mask); });
+    if (E > 0) run.template each<struct vg_cc_write_edge_stage>(E, STAGE_FN(long long i) { vg_cc_write_edge(g, i, pair_keep); });
+    return run.status;
+}
 
 }  // namespace
 
@@ -464,7 +510,6 @@ extern "C" int gtsfm_view_graph_cycle_filter_f64(const int32_t* pair_images_dev,
                                                  int num_images, int criterion, double error_threshold, long long triplet_capacity, void* workspace_dev,
                                                  size_t workspace_bytes, int32_t* num_triplets_dev, double* aggregate_error_dev, uint8_t* keep_dev,
                                                  int32_t* counts_dev, int32_t* triplets_dev, double* cycle_error_dev, long long* num_triplets_host, void* stream_) {
-    hipStream_t stream = (hipStream_t)stream_;
     const char* me = "gtsfm_view_graph_cycle_filter_f64";
     if (num_triplets_host) *num_triplets_host = -1;
     GTSFM_CHECK_ARG(num_edges >= 0 && num_edges < VG_MAX_EDGES && num_images >= 0 && num_images < VG_MAX_IMAGES && triplet_capacity >= 0 && triplet_capacity < VG_MAX_TRIPLETS,
@@ -472,122 +517,27 @@ extern "C" int gtsfm_view_graph_cycle_filter_f64(const int32_t* pair_images_dev,
     GTSFM_CHECK_ARG(criterion == 0 || criterion == 1, "%s: criterion %d is neither MIN_EDGE_ERROR (0) nor MEDIAN_EDGE_ERROR (1)", me, criterion);
     GTSFM_CHECK_ARG(counts_dev, "%s: null counts_dev", me);
     GTSFM_CHECK_ARG((triplets_dev == nullptr) == (cycle_error_dev == nullptr), "%s: triplets_dev and cycle_error_dev come together", me);
-    if (num_edges == 0) {
-        if (hipMemsetAsync(counts_dev, 0, 8 * sizeof(int32_t), stream) != hipSuccess) {
-            gtsfm_set_error("%s: hipMemsetAsync failed: %s", me, hipGetErrorString(hipGetLastError()));
-            return GTSFM_ERR_HIP;
-        }
-        if (num_triplets_host) *num_triplets_host = 0;
-        return GTSFM_OK;
-    }
-    GTSFM_CHECK_ARG(pair_images_dev && rotation_dev && workspace_dev && num_triplets_dev && aggregate_error_dev && keep_dev, "%s: null pointer", me);
-    GTSFM_CHECK_ARG(((uintptr_t)workspace_dev & 255) == 0, "%s: the workspace must be aligned to 256 bytes", me);
     VgGraph g{pair_images_dev, rotation_dev, pair_enable_dev, num_edges, num_images, vg_layout(workspace_dev, num_edges, num_images, triplet_capacity)};
-    if (workspace_bytes < g.w.bytes) {
-        gtsfm_set_error("%s: workspace of %zu bytes, %zu needed for %lld edges, %d images and %lld triplets", me, workspace_bytes, g.w.bytes, num_edges, num_images,
-                        triplet_capacity);
-        return GTSFM_ERR_WORKSPACE;
+    if (num_edges > 0) {  // without an edge the stages touch the counts only
+        GTSFM_CHECK_ARG(pair_images_dev && rotation_dev && workspace_dev && num_triplets_dev && aggregate_error_dev && keep_dev, "%s: null pointer", me);
+        const int fits = gtsfm_check_workspace(me, workspace_dev, workspace_bytes >= g.w.bytes, workspace_bytes, g.w.bytes, "%lld edges, %d images and %lld triplets", num_edges, num_images, triplet_capacity);
+        if (fits != GTSFM_OK) return fits;
     }
-    const dim3 threads(VG_THREADS), edge_grid = launch_grid(num_edges, VG_THREADS), slot_grid = launch_grid(2 * num_edges, VG_THREADS);
-    const long long init_n = (long long)num_images + 1 > VG_FLAG_WORDS ? (long long)num_images + 1 : VG_FLAG_WORDS;
-
-    hipLaunchKernelGGL(vg_init_kernel, launch_grid(init_n, VG_THREADS), threads, 0, stream, g, init_n);
-    GTSFM_CHECK_LAUNCH("vg_init_kernel");
-    hipLaunchKernelGGL(vg_edge_degree_kernel, edge_grid, threads, 0, stream, g);
-    GTSFM_CHECK_LAUNCH("vg_edge_degree_kernel");
-    hipLaunchKernelGGL(scan_one_workgroup_kernel<long long>, dim3(1), dim3(SCAN_THREADS), 0, stream, g.w.row_off, (long long)num_images);
-    GTSFM_CHECK_LAUNCH("scan_one_workgroup_kernel");
-    hipLaunchKernelGGL(vg_edge_fill_kernel, edge_grid, threads, 0, stream, g);
-    GTSFM_CHECK_LAUNCH("vg_edge_fill_kernel");
-    hipLaunchKernelGGL(vg_slot_rank_kernel, slot_grid, threads, 0, stream, g);
-    GTSFM_CHECK_LAUNCH("vg_slot_rank_kernel");
-    int flags[2] = {0, 0};
-    if (hipMemcpyAsync(flags, g.w.flags, sizeof(flags), hipMemcpyDeviceToHost, stream) != hipSuccess || hipStreamSynchronize(stream) != hipSuccess) {
-        gtsfm_set_error("%s: building the adjacency failed: %s", me, hipGetErrorString(hipGetLastError()));
-        return GTSFM_ERR_HIP;
-    }
-    GTSFM_CHECK_ARG(!flags[0], "%s: an enabled edge has i1 >= i2 or names an image outside 0 .. %d; nothing was written", me, num_images - 1);
-    GTSFM_CHECK_ARG(!flags[1], "%s: an enabled edge is listed twice; nothing was written", me);
-
-    hipLaunchKernelGGL(vg_slot_triplets_kernel, slot_grid, threads, 0, stream, g, 0, (int*)nullptr, (double*)nullptr);
-    GTSFM_CHECK_LAUNCH("vg_slot_triplets_kernel");
-    hipLaunchKernelGGL(scan_one_workgroup_kernel<long long>, dim3(1), dim3(SCAN_THREADS), 0, stream, g.w.seg_off, 2 * num_edges);
-    GTSFM_CHECK_LAUNCH("scan_one_workgroup_kernel");
-    hipLaunchKernelGGL(scan_one_workgroup_kernel<long long>, dim3(1), dim3(SCAN_THREADS), 0, stream, g.w.trip_off, 2 * num_edges);
-    GTSFM_CHECK_LAUNCH("scan_one_workgroup_kernel");
-    long long totals[2] = {-1, -1};  // entries of the per-edge lists, distinct triplets
-    if (hipMemcpyAsync(&totals[0], g.w.seg_off + 2 * num_edges, 8, hipMemcpyDeviceToHost, stream) != hipSuccess ||
-        hipMemcpyAsync(&totals[1], g.w.trip_off + 2 * num_edges, 8, hipMemcpyDeviceToHost, stream) != hipSuccess || hipStreamSynchronize(stream) != hipSuccess) {
-        gtsfm_set_error("%s: counting the triplets failed: %s", me, hipGetErrorString(hipGetLastError()));
-        return GTSFM_ERR_HIP;
-    }
-    GTSFM_CHECK_ARG(totals[1] >= 0 && totals[0] == 3 * totals[1], "%s: %lld list entries for %lld triplets; nothing was written", me, totals[0], totals[1]);
-    if (num_triplets_host) *num_triplets_host = totals[1];
-    if (totals[1] > triplet_capacity) {
-        gtsfm_set_error("%s: %lld triplets, capacity (workspace and triplet outputs) for %lld; nothing was written", me, totals[1], triplet_capacity);
-        return GTSFM_ERR_WORKSPACE;
-    }
-
-    hipLaunchKernelGGL(vg_slot_triplets_kernel, slot_grid, threads, 0, stream, g, 1, triplets_dev, cycle_error_dev);
-    GTSFM_CHECK_LAUNCH("vg_slot_triplets_kernel");
-    hipLaunchKernelGGL(vg_edge_aggregate_kernel, launch_grid(num_edges, VG_THREADS / VG_WAVE), threads, 0, stream, g, criterion, error_threshold, num_triplets_dev,
-                       aggregate_error_dev, keep_dev);
-    GTSFM_CHECK_LAUNCH("vg_edge_aggregate_kernel");
-    hipLaunchKernelGGL(vg_filter_counts_kernel, dim3(1), dim3(SCAN_THREADS), 0, stream, g.w.input, keep_dev, num_triplets_dev, num_edges, totals[1], counts_dev);
-    GTSFM_CHECK_LAUNCH("vg_filter_counts_kernel");
-    return GTSFM_OK;
+    DeviceRunner run{(hipStream_t)stream_, me};
+    return vg_cycle_filter_stages(run, me, g, criterion, error_threshold, triplet_capacity, num_triplets_dev, aggregate_error_dev, keep_dev, counts_dev, triplets_dev,
+                                  cycle_error_dev, num_triplets_host);
 }
 
 extern "C" int gtsfm_largest_component(const int32_t* pair_images_dev, const uint8_t* pair_enable_dev, long long num_edges, int num_images, void* workspace_dev,
                                        size_t workspace_bytes, uint8_t* node_mask_dev, uint8_t* pair_keep_dev, int32_t* counts_dev, void* stream_) {
-    hipStream_t stream = (hipStream_t)stream_;
     const char* me = "gtsfm_largest_component";
     GTSFM_CHECK_ARG(num_edges >= 0 && num_edges < VG_MAX_EDGES && num_images >= 0 && num_images < VG_MAX_IMAGES, "%s: sizes out of range (%lld edges, %d images)", me,
                     num_edges, num_images);
     GTSFM_CHECK_ARG(counts_dev && (num_images == 0 || node_mask_dev) && (num_edges == 0 || (pair_images_dev && pair_keep_dev)), "%s: null pointer", me);
-    GTSFM_CHECK_ARG(workspace_dev && ((uintptr_t)workspace_dev & 255) == 0, "%s: the workspace must be aligned to 256 bytes", me);
     VgComponents g = vg_cc_layout(workspace_dev, num_images);
     g.pair_images = pair_images_dev, g.pair_enable = pair_enable_dev, g.num_edges = num_edges, g.num_images = num_images;
-    if (workspace_bytes < g.bytes) {
-        gtsfm_set_error("%s: workspace of %zu bytes, %zu needed for %d images", me, workspace_bytes, g.bytes, num_images);
-        return GTSFM_ERR_WORKSPACE;
-    }
-    const dim3 threads(VG_THREADS), edge_grid = launch_grid(num_edges, VG_THREADS), node_grid = launch_grid(num_images, VG_THREADS);
-    const long long init_n = num_images > VG_FLAG_WORDS ? num_images : VG_FLAG_WORDS;
-    hipLaunchKernelGGL(vg_cc_init_kernel, launch_grid(init_n, VG_THREADS), threads, 0, stream, g, init_n);
-    GTSFM_CHECK_LAUNCH("vg_cc_init_kernel");
-    if (num_edges > 0) {
-        const auto hook = [&](int round) -> int {
-            hipLaunchKernelGGL(vg_cc_hook_kernel, edge_grid, threads, 0, stream, g, round);
-            GTSFM_CHECK_LAUNCH("vg_cc_hook_kernel");
-            return GTSFM_OK;
-        };
-        const auto compress = [&]() -> int {
-            hipLaunchKernelGGL(vg_cc_compress_kernel, node_grid, threads, 0, stream, g);
-            GTSFM_CHECK_LAUNCH("vg_cc_compress_kernel");
-            return GTSFM_OK;
-        };
-        int rounds = 0;
-        const UfOutcome labelled = uf_run_rounds(g.flags, stream, hook, compress, &rounds);
-        if (labelled == UF_LAUNCH_FAILED) return GTSFM_ERR_HIP;
-        if (labelled == UF_READ_FAILED) {
-            gtsfm_set_error("%s: round %d failed: %s", me, rounds, hipGetErrorString(hipGetLastError()));
-            return GTSFM_ERR_HIP;
-        }
-        GTSFM_CHECK_ARG(labelled != UF_NO_FIXED_POINT, "%s: no fixed point after %d rounds (%d images, %lld edges); nothing was written", me, rounds, num_images, num_edges);
-        GTSFM_CHECK_ARG(labelled != UF_BAD_INPUT, "%s: an enabled edge names an image outside 0 .. %d; nothing was written", me, num_images - 1);
-    }
-    if (num_edges > 0) {
-        hipLaunchKernelGGL(vg_cc_node_count_kernel, node_grid, threads, 0, stream, g);
-        GTSFM_CHECK_LAUNCH("vg_cc_node_count_kernel");
-    }
-    hipLaunchKernelGGL(vg_cc_summary_kernel, dim3(1), dim3(SCAN_THREADS), 0, stream, g, counts_dev);
-    GTSFM_CHECK_LAUNCH("vg_cc_summary_kernel");
-    hipLaunchKernelGGL(vg_cc_write_node_kernel, node_grid, threads, 0, stream, g, node_mask_dev);
-    GTSFM_CHECK_LAUNCH("vg_cc_write_node_kernel");
-    if (num_edges > 0) {
-        hipLaunchKernelGGL(vg_cc_write_edge_kernel, edge_grid, threads, 0, stream, g, pair_keep_dev);
-        GTSFM_CHECK_LAUNCH("vg_cc_write_edge_kernel");
-    }
-    return GTSFM_OK;
+    const int fits = gtsfm_check_workspace(me, workspace_dev, workspace_bytes >= g.bytes, workspace_bytes, g.bytes, "%d images", num_images);
+    if (fits != GTSFM_OK) return fits;
+    DeviceRunner run{(hipStream_t)stream_, me};
+    return vg_largest_component_stages(run, me, g, node_mask_dev, pair_keep_dev, counts_dev);
 }

@@ -47,7 +47,29 @@ def longdouble_distance(sc, world_pair) -> float:
 
 @pytest.mark.parametrize("name", scenes.SCENE_NAMES)
 def test_scene_is_byte_equal_to_the_restatement(engine, name):
-    sc, exp = scenes.get(name), scenes.expected(name)
+    held_to_the_restatement(engine, name, scenes.get(name), scenes.expected(name))
+
+
+def rows_256_scene():
+    """150 pair rows and 106 measurement rows: num_pairs + num_meas is exactly one workgroup of the per-row stages, and the last row is a
+    measurement."""
+    rng = np.random.default_rng(61)
+    centre, rot, _, tracks = scenes.true_geometry(rng, 40, 53, per_landmark=2)
+    pairs = scenes.window(40, 4)
+    sc = scenes.scene("rows_256", pairs, scenes.pair_directions(centre, rot, pairs), 40, scenes.random_units(rng, 3), rotation=rot, tracks=tracks,
+                      uv=rng.uniform(0, 100, size=(106, 2)))
+    assert (len(sc["pair_images"]), len(sc["image"])) == (150, 106)
+    return sc
+
+
+def test_row_count_of_exactly_one_workgroup(engine):
+    sc = rows_256_scene()
+    exp = scenes.restate(sc)
+    assert exp["counts"][0] == 150 and exp["counts"][1] == 106 and 0 < exp["counts"][3] and 0 < exp["counts"][4]  # every row is an edge, both kinds have inliers
+    held_to_the_restatement(engine, sc["name"], sc, exp)
+
+
+def held_to_the_restatement(engine, name, sc, exp):
     got = run_scene(engine, sc)
     limit = 2048 if sc["lds_node_limit"] < 0 else min(sc["lds_node_limit"], 2048)  # TR_LDS_NODES is the default and the most
     assert got["tier"] == ("workspace" if int(exp["counts"][2]) > limit else "lds")

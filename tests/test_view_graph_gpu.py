@@ -58,6 +58,30 @@ def test_scene_against_the_restatement(engine, name):
         print(f"{name}: " + ", ".join(f"{k} {v}" for k, v in tol.items() if k not in ("restatement", "tolerance", "exact_zero")))
 
 
+def boundary_scene(edges):
+    """Exactly ``edges`` enabled edges: window(130, 2) has 257, in lexicographic order, so its first rows are a window graph too."""
+    sc = scenes.scene(f"window_{edges}", scenes.window(130, 2)[:edges], seed=8)
+    assert len(sc["pair_images"]) == edges and sc["enable"] is None
+    scenes.check_scene(sc)
+    return sc
+
+
+@pytest.mark.parametrize("edges", [255, 256, 257])
+def test_edge_counts_around_one_workgroup(engine, edges):
+    """255, 256 and 257 edges: one lane short of a full workgroup of the per-edge stages, exactly one, and one lane into the second (510, 512
+    and 514 slots for the per-slot stages, 64 and 65 workgroups of four waves for the aggregate). Both criteria, then the largest component
+    of the kept edges, held to the restatement by the rule of every other scene."""
+    sc = boundary_scene(edges)
+    tol = scenes.measured_tolerance()
+    for criterion in (ref.MIN_EDGE_ERROR, ref.MEDIAN_EDGE_ERROR):
+        exp = ref.cycle_filter(sc["pair_images"], sc["rotation"], None, sc["num_images"], criterion, 7.0)
+        exp["component"] = ref.largest_component(sc["pair_images"], exp["keep"], sc["num_images"])
+        assert 0 < exp["keep"].sum() < edges and len(exp["triplets"]) > 100  # the filter and the component have something to decide
+        got = run_scene(engine, sc, criterion, 7.0)
+        assert len(got["keep"]) == edges
+        scenes.check_outputs(f"{sc['name']}/{criterion}", got, exp, tol["tolerance"], exact_zero=tol["exact_zero"])
+
+
 @pytest.mark.parametrize("name", [n for n in SCENE_NAMES if n not in ("empty", "one_edge")])
 def test_row_permutation_and_rerun_are_byte_equal(engine, name):
     sc = {s["name"]: s for s in scenes.all_scenes()}[name]

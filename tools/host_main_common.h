@@ -42,25 +42,10 @@ void fill_vector(std::vector<T>& v, size_t n, int fill) {
     v.resize(n);
 }
 
-// f(i) for i in 0 .. n - 1, ascending or descending
-template <class F>
-void walk(long long n, bool descending, F f) {
-    if (descending) {
-        for (long long i = n - 1; i >= 0; --i) f(i);
-    } else {
-        for (long long i = 0; i < n; ++i) f(i);
-    }
-}
-
-// val[0 .. n) -> its exclusive prefix sum in place, val[n] = the total, by a plain loop
-void exclusive_scan(long long* val, long long n) {
-    long long run = 0;
-    for (long long i = 0; i < n; ++i) {
-        const long long x = val[i];
-        val[i] = run;
-        run += x;
-    }
-    val[n] = run;
+// the exit status for a pipeline's refusal; its reason is on stderr already (gtsfm_set_error)
+int refused(int status) {
+    fprintf(stderr, "refused (status %d)\n", status);
+    return 3;
 }
 
 template <class T>

@@ -1,5 +1,5 @@
-// Stand-alone host build of the 1DSfM kernels' per-lane functions (the GTSFM_HD functions of gtsfm_amd/csrc/translation_kernels.hip: the edge
-// table, the adjacency, the MFAS ordering, the per-row aggregate), for running them on a CPU and under the host sanitizers:
+// Stand-alone host build of the 1DSfM call (tr_inliers_stages of gtsfm_amd/csrc/translation_kernels.hip: the very stage sequence the device
+// call launches, over the same GTSFM_HD per-lane functions), for running it on a CPU and under the host sanitizers:
 //
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off [-Xarch_host -fsanitize=address,undefined] -c tools/translation_inliers_host_main.cpp -o main.o
 //   hipcc [-fsanitize=address,undefined] main.o -o translation_inliers_host
@@ -11,7 +11,8 @@
 // world_pair[3 E], double world_meas[3 S] (read as inputs with directions_given). out.bin: two copies (see below) of double world_pair[3 E],
 // world_meas[3 S], pair_weight[E], meas_weight[S], uint8 pair_inlier[E], meas_inlier[S], camera_inlier[N], int32 position[D (N + T)], counts[8].
 //
-// The stages are the device call's, each a loop over the indices its kernel covers, the prefix sums by a plain loop. They run twice. First
+// The stages are the device call's own (tr_inliers_stages), walked by the HostRunner of gtsfm_amd/csrc/stage_runner.h: each a loop over the
+// indices its kernel covers, the prefix sums and the block-cooperative kernels by the plain loops written next to them. They run twice. First
 // every stage walks its indices in ASCENDING order and ONE lane does the whole ordering of a direction, over a workspace and outputs filled
 // with zeros. Then every stage walks its indices in DESCENDING order and the ordering is done by the device's 256-lane partition, the last
 // lane first, over memory filled with 0xFF. The atomics are plain updates here, so the two runs hand out the list slots in opposite orders.
@@ -61,8 +62,9 @@ struct Outputs {
     std::vector<int> position, counts;
 };
 
-// 0: done; 3: refused
-int run(const Scene& s, bool descending, int lanes, int fill, Outputs& out) {
+// the call's stages over memory filled with `fill`: the pipeline's status
+int run(const Scene& s, HostRunner runner, int fill, Outputs& out) {
+    const char* me = "translation_inliers_host";
     const long long E = s.E, S = s.S, N = s.N, T = s.T, D = s.D, rows = E + S, nodes = N + T;
     fill_vector(out.world_pair, 3 * E, fill), fill_vector(out.world_meas, 3 * S, fill), fill_vector(out.pair_weight, E, fill), fill_vector(out.meas_weight, S, fill);
     fill_vector(out.pair_inlier, E, fill), fill_vector(out.meas_inlier, S, fill), fill_vector(out.camera_inlier, N, fill), fill_vector(out.position, D * nodes, fill);
@@ -71,63 +73,15 @@ int run(const Scene& s, bool descending, int lanes, int fill, Outputs& out) {
         if (E) memcpy(out.world_pair.data(), s.world_pair, 3 * E * 8);
         if (S) memcpy(out.world_meas.data(), s.world_meas, 3 * S * 8);
     }
-    if (D <= 0 && rows > 0) {
-        fprintf(stderr, "refused: no projection direction\n");
-        return 3;
-    }
-    if (S > 0 && T <= 0) {
-        fprintf(stderr, "refused: measurements without tracks\n");
-        return 3;
-    }
-    const size_t bytes = tr_layout(nullptr, rows, nodes, D, nodes, 0).bytes;  // lds_node_limit 0: the state slices exist
-    void* ws = filled(bytes, fill);
-    TrGraph g{s.pair_images, s.pair_direction, s.has_pair_enable ? s.pair_enable : nullptr, s.rotation, s.rotation_valid, s.intrinsics, s.track_off, s.image, s.uv,
-              s.track_enable, s.has_meas_enable ? s.meas_enable : nullptr, s.directions, E, S, T, D, (int)N, s.directions_given ? 1 : 0, out.world_pair.data(),
-              out.world_meas.data(), tr_layout(ws, rows, nodes, D, nodes, 0)};
-    const long long init_n = nodes + 1 > TR_FLAG_WORDS ? nodes + 1 : TR_FLAG_WORDS;
-    walk(init_n, descending, [&](long long i) { tr_init(g, i, out.camera_inlier.data()); });
-    walk(rows, descending, [&](long long i) { tr_edge_table(g, i); });
-    walk(nodes, descending, [&](long long i) { tr_node_flag(g, i); });
-    exclusive_scan(g.w.row_off, nodes);
-    exclusive_scan(g.w.cid, nodes);
-    walk(nodes + 1, descending, [&](long long i) { tr_node_compact(g, i, nodes); });
-    walk(rows, descending, [&](long long i) { tr_edge_fill(g, i); });
-    walk(2 * rows, descending, [&](long long i) { tr_slot_rank(g, i); });
-    for (int k = 0; k < 4; ++k) {
-        if (g.w.flags[k]) {
-            const char* why[4] = {"a bad pair", "a duplicate measurement", "a camera out of range", "a camera without a rotation"};
-            fprintf(stderr, "refused: %s\n", why[k]);
-            free(ws);
-            return 3;
-        }
-    }
-    const int num_nodes = (int)g.w.cid[nodes];
-    std::vector<TrKey> keys(lanes);
-    walk(D, descending, [&](long long k) {
-        double* base = g.w.state;  // one "workgroup" at a time: the first slice
-        const TrState st = {base, base + num_nodes, base + 2 * (size_t)num_nodes, g.w.pos + k * num_nodes};
-        const double* d = g.directions + 3 * k;
-        walk(lanes, descending, [&](long long lane) { tr_mfas_init_lane(g, st, d, num_nodes, (int)lane, lanes); });
-        for (int step = 0; step < num_nodes; ++step) {
-            walk(lanes, descending, [&](long long lane) { keys[lane] = tr_mfas_lane_best(st, num_nodes, (int)lane, lanes); });
-            TrKey key = keys[descending ? lanes - 1 : 0];
-            walk(lanes, descending, [&](long long lane) { key = tr_key_max(key, keys[lane]); });
-            if (key.id < num_nodes) walk(lanes, descending, [&](long long lane) { tr_mfas_update_lane(g, st, d, key.id, step, (int)lane, lanes); });
-        }
-    });
-    walk(rows, descending, [&](long long i) {
-        tr_row_aggregate(g, i, num_nodes, s.threshold, out.pair_weight.data(), out.meas_weight.data(), out.pair_inlier.data(), out.meas_inlier.data(),
-                         out.camera_inlier.data());
-    });
-    walk(S, descending, [&](long long i) { tr_meas_filter(g, i, out.camera_inlier.data(), out.meas_inlier.data()); });
-    memset(out.counts.data(), 0, 8 * sizeof(int));  // tr_counts_kernel: integer sums over the rows
-    out.counts[2] = num_nodes;
-    walk(E, descending, [&](long long m) { out.counts[0] += g.w.key1[m] >= 0 ? 1 : 0, out.counts[3] += out.pair_inlier[m] ? 1 : 0; });
-    walk(S, descending, [&](long long m) { out.counts[1] += g.w.key1[E + m] >= 0 ? 1 : 0, out.counts[4] += out.meas_inlier[m] ? 1 : 0; });
-    walk(N, descending, [&](long long c) { out.counts[5] += out.camera_inlier[c] ? 1 : 0; });
-    walk(D * nodes, descending, [&](long long i) { tr_position_out(g, i, num_nodes, out.position.data()); });
+    GTSFM_CHECK_ARG(S == 0 || T > 0, "%s: measurements without tracks", me);
+    void* ws = filled(tr_layout(nullptr, rows, nodes, D, nodes, 0).bytes, fill);  // lds_node_limit 0: the state slices exist
+    const TrGraph g{s.pair_images, s.pair_direction, s.has_pair_enable ? s.pair_enable : nullptr, s.rotation, s.rotation_valid, s.intrinsics, s.track_off, s.image, s.uv,
+                    s.track_enable, s.has_meas_enable ? s.meas_enable : nullptr, s.directions, E, S, T, D, (int)N, s.directions_given ? 1 : 0, out.world_pair.data(),
+                    out.world_meas.data(), tr_layout(ws, rows, nodes, D, nodes, 0)};
+    const int status = tr_inliers_stages(runner, me, g, s.threshold, nodes, 0, out.pair_weight.data(), out.meas_weight.data(), out.pair_inlier.data(),
+                                         out.meas_inlier.data(), out.camera_inlier.data(), out.position.data(), out.counts.data());
     free(ws);
-    return 0;
+    return status;
 }
 
 bool write_outputs(FILE* f, const Outputs& o) {
@@ -148,11 +102,11 @@ int main(int argc, char** argv) {
         return 1;
     }
     Outputs first, second;
-    int rc = run(s, false, 1, 0x00, first);
-    if (rc == 0) rc = run(s, true, TR_THREADS, 0xFF, second);
+    int status = run(s, HostRunner{false, false}, 0x00, first);
+    if (status == GTSFM_OK) status = run(s, HostRunner{true, true}, 0xFF, second);
     free(s.pair_images), free(s.pair_direction), free(s.pair_enable), free(s.rotation), free(s.rotation_valid), free(s.intrinsics), free(s.track_off), free(s.image);
     free(s.uv), free(s.track_enable), free(s.meas_enable), free(s.directions), free(s.world_pair), free(s.world_meas);
-    if (rc) return rc;
+    if (status != GTSFM_OK) return refused(status);
     FILE* f = fopen(argv[2], "wb");
     if (!f || !write_outputs(f, first) || !write_outputs(f, second) || fclose(f) != 0) {
         fprintf(stderr, "cannot write %s\n", argv[2]);

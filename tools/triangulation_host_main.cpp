@@ -9,11 +9,12 @@
 // int32 image[S], float uv[2 S], double cameras[17 num_images]. out.bin: two copies (one per lane partition, see below) of double
 // point[3 T], double avg_error[T], int32 exit_code[T], uint8 inlier_mask[S], int32 stats[4 T].
 //
-// The stages are the device call's: count -> serial scan -> select -> hypothesis -> final. They run twice: with one lane doing all the
-// work (first 0, stride 1) over a zeroed workspace, and with the device's partition (select: 256 lanes per track; hypothesis: a grid
-// of min(ceil(cap / 256), 2048) x 256 lanes, grid-stride) over a workspace filled with 0xFF. The two outputs must be byte-equal: exit
-// status 2 when they are not, 3 / 4 for the two error flags of the device call (nothing written), 1 for a bad file. Every input array
-// is a heap allocation of its exact size, so a read outside it is a sanitizer report.
+// The stages are the device call's own (tri_triangulate_stages), walked by the HostRunner of gtsfm_amd/csrc/stage_runner.h. They run
+// twice: ascending with one lane per group (select: one lane per track; hypothesis: min(ceil(cap / 256), 2048) lanes, grid-stride) over a
+// zeroed workspace, and descending with the device's partition (256 lanes per track; a grid of that many groups x 256 lanes, the last
+// lane first) over a workspace filled with 0xFF. The two outputs must be byte-equal: exit status 2 when they are not, 3 when the call
+// refuses its input (an error flag of the device call; nothing written), with the reason on stderr, 1 for a bad file. Every input array is
+// a heap allocation of its exact size, so a read outside it is a sanitizer report.
 
 #include "../gtsfm_amd/csrc/triangulation_kernels.hip"
 #include "host_main_common.h"
@@ -75,33 +76,14 @@ struct Outputs {
     }
 };
 
-// 0, or the error flag's exit status
-int run(const Scene& s, bool device_partition, Outputs& out) {
+// the call's stages over a workspace filled with `fill`: the pipeline's status
+int run(const Scene& s, HostRunner runner, int fill, Outputs& out) {
     const int mode = (int)s.mode;
     const long long max_hyp = mode == TRI_NO_RANSAC ? 0 : s.num_hyp;
-    const size_t bytes = tri_layout(nullptr, s.num_tracks, s.total, max_hyp).bytes;
-    void* base = filled(bytes, device_partition ? 0xFF : 0x00);
-    if (!base) return 1;
-    const TriWorkspace w = tri_layout(base, s.num_tracks, s.total, max_hyp);
-    memset(w.flags, 0, 16);
-    for (long long t = 0; t < s.num_tracks; ++t) tri_count_track(t, s.track_off, s.num_tracks, s.total, mode, max_hyp, w.hyp_off, w.flags);
-    exclusive_scan(w.hyp_off, s.num_tracks);  // the scan kernel, serially
-    if (w.hyp_off[s.num_tracks] > w.cap) w.flags[1] = 1;
-    if (mode != TRI_NO_RANSAC) {
-        const int select_lanes = device_partition ? TRI_THREADS : 1;
-        for (long long t = 0; t < s.num_tracks; ++t)
-            for (int lane = 0; lane < select_lanes; ++lane)
-                tri_select_track(t, lane, select_lanes, s.track_off, s.image, s.uv, s.cams, (int)s.num_images, mode, max_hyp, s.seed, w.hyp_off, w.sel, w.cap, w.flags);
-        const long long want = (w.cap + TRI_THREADS - 1) / TRI_THREADS;
-        const long long lanes = device_partition ? (want < TRI_HYP_BLOCKS ? want : TRI_HYP_BLOCKS) * TRI_THREADS : 1;
-        for (long long lane = 0; lane < lanes; ++lane)
-            tri_hypothesis_lane(lane, lanes, s.track_off, s.image, s.uv, s.num_tracks, s.cams, (int)s.num_images, s.threshold, max_hyp, w.hyp_off, w.sel, w.hyp, w.cap,
-                                w.flags);
-    }
-    for (long long t = 0; t < s.num_tracks; ++t)
-        tri_final_track(t, s.track_off, s.image, s.uv, s.num_tracks, s.cams, (int)s.num_images, mode, s.threshold, s.min_angle, w.hyp_off, w.hyp, w.cap, w.flags,
-                        out.point.data(), out.avg.data(), out.code.data(), out.mask.data(), out.stats.data());
-    const int status = w.flags[0] ? 3 : (w.flags[1] ? 4 : 0);
+    void* base = filled(tri_layout(nullptr, s.num_tracks, s.total, max_hyp).bytes, fill);
+    const TriCall c{s.track_off, s.image, s.uv, s.num_tracks, s.total, s.cams, (int)s.num_images, mode, s.threshold, s.min_angle, max_hyp, s.seed, out.point.data(),
+                    out.avg.data(), out.code.data(), out.mask.data(), out.stats.data()};
+    const int status = tri_triangulate_stages(runner, "triangulation_host", c, tri_layout(base, s.num_tracks, s.total, max_hyp));
     free(base);
     return status;
 }
@@ -125,9 +107,8 @@ int main(int argc, char** argv) {
     Outputs serial(s), device(s);
     int status = 0;
     if (s.num_tracks > 0) {
-        status = run(s, false, serial);
-        const int second = run(s, true, device);
-        if (status != second) status = 2;
+        const int first = run(s, HostRunner{false, false}, 0x00, serial), second = run(s, HostRunner{true, true}, 0xFF, device);
+        status = first != second ? 2 : (first != GTSFM_OK ? refused(first) : 0);
     }
     if (status == 0 && !serial.same(device)) {
         fprintf(stderr, "the outputs depend on the lane partition or on what the workspace held\n");
