@@ -28,6 +28,14 @@ def empty_triangulation() -> Dict[str, Any]:  # and what ``triangulate`` does
             "exit_code": np.zeros(0, np.int32), "inlier_mask": np.zeros(0, np.uint8)}
 
 
+def empty_bundle_adjustment() -> Dict[str, Any]:  # and what ``bundle_adjust`` does
+    from gtsfm_amd.runtime.global_ba_engine import COST_FIELDS, COUNTER_FIELDS, NO_VALID_ROW
+
+    return {"track_off": np.zeros(1, np.int64), "image": np.zeros(0, np.int32), "kp": np.zeros(0, np.int32), "point": np.zeros((0, 3)), "cameras": np.zeros((0, 17)),
+            "track_valid": np.zeros(0, np.uint8), "camera_kept": np.zeros(0, np.uint8), "reproj_error": np.zeros(0), "exit_code": np.zeros(0, np.int32),
+            "counters": dict(dict.fromkeys(COUNTER_FIELDS, 0), status=NO_VALID_ROW, anchor=-1), "costs": dict.fromkeys(COST_FIELDS, float("nan")), "status": "NO_VALID_ROW"}
+
+
 class ViewGraph:
     """What ``VerifiedScene.view_graph`` returns. ``pairs``: the scene's edge rows (the launches' pairs, then the edges of ``extra``);
     ``edges``: the view-graph edges, those every pass kept, in row order; ``pruned_edges``: those of them in the largest connected
@@ -428,6 +436,38 @@ class VerifiedScene:
         trk = self._tracks_on_device(edges)
         out = Point3dInitializer(cameras, options, seed=seed, device=self.feats["xy"].device).triangulate_arrays(trk["track_off"], trk["image"], trk["uv"])
         return {**{k: trk[k].cpu().numpy() for k in ("track_off", "image", "kp")}, **{k: out[k].cpu().numpy() for k in ("point", "avg_error", "exit_code", "inlier_mask")}}
+
+    def bundle_adjust(self, cameras: Dict[int, Any], triangulation_options, optimizer=None, edges: Optional[Iterable[Tuple[int, int]]] = None, seed: int = 0) -> Dict[str, Any]:
+        """Tracks -> triangulation -> global bundle adjustment (``gtsfm/multi_view_optimizer.py:200-221``: ``DataAssociation`` then
+        ``bundle_adjustment_module``) on the device arrays where they lie: the track CSR the track builder writes and the points, exit
+        codes and inlier mask the triangulation writes are the adjustment's inputs; no track, point or mask is downloaded in between.
+        ``optimizer``: a ``BundleAdjustmentOptimizer`` (None: ``unified.yaml``'s). A track takes part when its exit code is SUCCESS, a
+        measurement when the triangulation kept it. Returns host arrays: the track CSR (``track_off``, ``image``, ``kp``), ``point``
+        [T, 3], ``cameras`` [N, 17], ``track_valid`` [T], ``camera_kept`` [N], ``reproj_error`` [S], ``exit_code`` [T], ``counters`` and
+        ``costs`` by name, ``status``."""
+        from gtsfm_amd.bundle.bundle_adjustment import BundleAdjustmentOptimizer, RobustBAMode
+        from gtsfm_amd.data_association.point3d_initializer import Point3dInitializer
+        from gtsfm_amd.runtime.global_ba_engine import COST_FIELDS, COUNTER_FIELDS
+
+        if self.feats is None:
+            return empty_bundle_adjustment()
+        import torch
+
+        optimizer = optimizer or BundleAdjustmentOptimizer(reproj_error_thresholds=(10, 5, 3), robust_ba_mode=RobustBAMode.HUBER, measurement_noise_sigma=1.0)
+        device = self.feats["xy"].device
+        trk = self._tracks_on_device(edges)
+        initializer = Point3dInitializer(cameras, triangulation_options, seed=seed, device=device)
+        tri = initializer.triangulate_arrays(trk["track_off"], trk["image"], trk["uv"])
+        from gtsfm_amd.runtime.triangulation_engine import pack_cameras
+
+        table = torch.from_numpy(pack_cameras(cameras, num_images=int(self.feats["xy"].shape[0]))).to(device)
+        track_enable = (tri["exit_code"] == 0).to(torch.uint8).contiguous()
+        out = optimizer.run_ba_device(table, trk["track_off"].contiguous(), trk["image"].contiguous(), trk["uv"].contiguous(), tri["point"].contiguous(), track_enable,
+                                      tri["inlier_mask"].contiguous())
+        return {**{k: trk[k].cpu().numpy() for k in ("track_off", "image", "kp")}, "point": out["point"].cpu().numpy(), "cameras": out["cameras"][0].cpu().numpy(),
+                "track_valid": out["track_valid"].cpu().numpy(), "camera_kept": out["camera_kept"][0].cpu().numpy(), "reproj_error": out["reproj_error"].cpu().numpy(),
+                "exit_code": tri["exit_code"].cpu().numpy(), "counters": named(out["counters"][0], COUNTER_FIELDS), "costs": named(out["costs"][0], COST_FIELDS, float),
+                "status": out["status"][0]}
 
     def tracks_2d(self, edges: Optional[Iterable[Tuple[int, int]]] = None) -> list:
         """The same tracks as ``SfmTrack2d`` objects over ``keypoints_list``'s coordinates."""

@@ -942,6 +942,59 @@ int gtsfm_translation_recovery_f64(const int32_t* pair_images_dev, const double*
                                    int max_inner, void* workspace_dev, size_t workspace_bytes, double* translation_out_dev, uint8_t* node_valid_dev,
                                    int32_t* counters_dev, double* costs_dev, void* stream);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * Global bundle adjustment (float64)
+ *   replaces gtsfm/bundle/bundle_adjustment.py (BundleAdjustmentOptimizer.run_ba: the factor graph, Levenberg-Marquardt and the
+ *   reprojection-error filter of gtsfm/common/gtsfm_data.py), called from gtsfm/multi_view_optimizer.py:215-221 after the triangulation.
+ * The inputs are the arrays gtsfm_triangulate_tracks_f64 reads and writes: cameras_dev [num_images][17] (valid, fx, fy, cx, cy, wRc
+ * row-major, wtc), the track CSR (track_off_dev [T + 1], image_dev [S], uv_dev [S][2] float32), point_dev [T][3]; track_enable_dev [T] and
+ * meas_enable_dev [S] uint8 (NULL: every one; in the chain exit_code == SUCCESS and the triangulation's inlier_mask). A measurement is VALID
+ * when it is enabled, its camera id lies in the table with valid != 0 and its pixel is finite; a track when it is enabled, its point is
+ * finite and it has at least min_track_length valid measurements; a measurement counts only in a valid track. A camera id outside the
+ * table counts as not estimated, it is no refusal. Refused (GTSFM_ERR_INVALID, gtsfm_last_error, no output written): track or problem
+ * offsets that are not ascending over their whole range, a problem with more than max_problem_tracks tracks.
+ * Camera i is node i, track j of a problem whose first track is t0 is node num_images + (j - t0). The problem is the connected component
+ * of `anchor` (a camera; -1: the smallest camera id with a valid measurement) over the valid measurements; every camera and point outside it
+ * is copied through unchanged with node_valid 0. The cost is f = sum_m rho_k(|proj(cam_i, p_j) - uv_m| / measurement_sigma) with gtsam's
+ * Huber on the norm (huber_k <= 0 or inf: the half square); a measurement whose point has depth <= 0 contributes zero residual and Jacobian.
+ * Calibrations are held fixed, the anchor's pose is held fixed exactly, the scale is left to the damping. A pose moves by (R Cay(omega),
+ * t + R v), a point by its 3-vector. Levenberg-Marquardt with the two-view call's scalar rules: lambda from 1e-5 by factors of 10 up to 1e5
+ * (beyond: LAMBDA_BOUND), a trial accepted when its cost is finite, the model decrease positive and the gain ratio > 1e-3; CONVERGED when an
+ * accepted step lowers the cost by less than abs_tol or relatively by less than rel_tol; at most max_iterations accepted steps. The linear
+ * step: every point's damped 3 x 3 block eliminated, the reduced camera system applied matrix-free and solved by conjugate gradients
+ * preconditioned by the cameras' damped 6 x 6 blocks, to |r| <= cg_forcing |r0|, r.M^-1 r <= 0 or max_inner iterations (0: six per camera); the points by
+ * back-substitution; the model decrease of the step actually taken by one more pass. Sums run over a node's measurements in ascending
+ * (neighbour, measurement) order and over the nodes by a fixed pairwise tree, so every byte is fixed by the inputs: not by the lane count,
+ * the run, or the problem's place in a batch. The specification is tests/global_ba_reference.py, operation for operation.
+ * Batch: problem_off_dev [P + 1] int64 over the tracks, from 0 to num_tracks (NULL with num_problems 1 and max_problem_tracks = num_tracks);
+ * the problems share the camera table and each refines a copy of its own; one workgroup solves one problem.
+ * PARITY UNPINNED towards the reference (nothing of gtsam was observed running): gtsam's Levenberg-Marquardt path, elimination ordering and
+ * retraction; the Karcher-mean factor and the soft prior (sigma 0.1) in place of the hard anchor; calibration variables, their priors and
+ * shared_calib; GNC / GMC / TLS; relative and absolute pose priors; the marginals check; select_largest_connected_component (here: the
+ * anchor's component); the metrics group.
+ * ---------------------------------------------------------------------------------------------------------- */
+
+/* Bytes of device workspace (0 for sizes out of range: negative, 2^28 measurements, 2^24 nodes, 2^28 nodes over all problems,
+ * max_problem_tracks > num_tracks): about 377 per measurement and 900 per node and problem, nodes = num_images + max_problem_tracks. One
+ * workgroup solves one problem, start to end: a call's time grows with measurements x CG iterations on ONE CU. */
+size_t gtsfm_global_ba_workspace_bytes(long long num_meas, long long num_images, long long num_tracks, long long max_problem_tracks, long long num_problems);
+
+/* Outputs, M = num_images + max_problem_tracks: cameras_out_dev [P][num_images][17], point_out_dev [T][3], reproj_error_dev [S] (pixels at
+ * the final values; NaN where the measurement is not a valid one of the problem or the point is behind the camera), track_valid_dev [T]
+ * uint8 (in the problem and every valid measurement's error finite and < reproj_error_threshold), camera_kept_dev [P][num_images] uint8 (a
+ * valid measurement in a kept track), node_valid_dev [P][M] uint8, counters_dev [P][8] int32 = status (0 CONVERGED, 1 MAX_ITERATIONS,
+ * 2 NO_VALID_ROW, 3 NON_FINITE: a first cost that is NaN, 4 LAMBDA_BOUND; on 2 and 3 the outputs are the inputs and the masks zero), anchor,
+ * cameras and points in the problem, valid measurements, accepted steps, linear solves tried, CG iterations; costs_dev [P][4] float64 = the
+ * initial cost, the final cost, the final |g|_inf, the final lambda. The call waits for the stream once, for the two refusal flags; the
+ * inputs are not changed. */
+int gtsfm_global_ba_f64(const double* cameras_dev, int num_images, const long long* track_off_dev, const int32_t* image_dev, const float* uv_dev,
+                        const double* point_dev, const uint8_t* track_enable_dev, const uint8_t* meas_enable_dev, long long num_tracks, long long num_meas,
+                        const long long* problem_off_dev, int num_problems, long long max_problem_tracks, int anchor, int min_track_length,
+                        double measurement_sigma, double huber_k, double reproj_error_threshold, double rel_tol, double abs_tol, double cg_forcing,
+                        int max_iterations, int max_inner, void* workspace_dev, size_t workspace_bytes, double* cameras_out_dev, double* point_out_dev,
+                        double* reproj_error_dev, uint8_t* track_valid_dev, uint8_t* camera_kept_dev, uint8_t* node_valid_dev, int32_t* counters_dev,
+                        double* costs_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
